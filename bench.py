@@ -9,10 +9,12 @@ contact), h = 1/180, with a flap — the last `--fold-rows` grid rows — folded
 contacts (detection, layering, layered friction and its transpose in the adjoint all run). 256 independent rollouts in total
 (per-rollout start offset and friction coefficient, seed = global rollout id), sharded over the ranks.
 One "step" = one forward time step (Simulation::step) + one backward step (Simulation::stepBackward) of all rollouts of the
-job; `value` = rollout-steps per second over the whole job = B_total * K / t.
+job; `value` = rollout-steps per second over the whole job = B_total * K / t. The K timed steps run as forward + backward sweeps of at most
+TIMED_WINDOW steps from the warmed-up state (the cost of a step grows along a longer rollout; see TIMED_WINDOW).
 
 Launch:  python bench.py --gpus 1 --steps K --warmup W
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+         --dump-outputs DIR: also write what the timed steps returned as DIR/<name>.npy, to compare two builds output for output
 One process per GPU; rollouts are independent, so ranks share nothing on the data path. Default: the metric's batch of 256
 rollouts is SHARDED over the ranks ("strong" scaling: 256 / N per GPU; with fewer rollouts than CUs the engine spreads each
 rollout over several workgroups, diffcloth_hip.h: dc_get_cluster). `--batch B` instead gives every rank B rollouts ("weak").
@@ -34,6 +36,9 @@ sys.path.insert(0, ROOT)
 from diffcloth_amd import workloads  # noqa: E402  (the workload definitions live in the package; tests/ is only imported by cpu_baseline)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
+# Default length of the CPU baseline sample. A fp64 step of one rollout on the host takes ~0.7 s, ~27 x a timed GPU step of the whole
+# batch, so a sample as long as the timed window would make the run's length grow with --steps far beyond the timed steps themselves.
+CPU_SAMPLE_STEPS = 5
 
 
 def scene(args):
@@ -63,8 +68,8 @@ rollout_inputs = workloads.c4_rollout_inputs      # per-rollout start state and 
 
 
 def cpu_baseline(args, V, F, center, field, x0, v0, mu, steps, gscale):
-    """Reference algorithm (fp64 oracle port, OpenMP at the reference's sites) on the host cores: the SAME window of steps of
-    rollout 0 as the GPU timed, forward and backward, direct adjoint solve (solveDirect semantics) like adjoint_mode 1."""
+    """Reference algorithm (fp64 oracle port, OpenMP at the reference's sites) on the host cores: the first `steps` of the steps of
+    rollout 0 the GPU timed, forward and backward, direct adjoint solve (solveDirect semantics) like adjoint_mode 1."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))      # the oracle's ctypes wrapper (test infrastructure) — the checker, timed here as the CPU baseline
     import orc
     threads = args.cpu_threads if args.cpu_threads > 0 else min(os.cpu_count() or 1, 32)
@@ -87,8 +92,8 @@ def cpu_baseline(args, V, F, center, field, x0, v0, mu, steps, gscale):
         gx, gv = b["dL_dx"], b["dL_dv"]
     dt = time.perf_counter() - t0
     return dict(value=steps / dt, unit="rollout-steps/s", cores=threads, kind="port",
-                sample=f"rollout 0 of this job from its state after the {args.warmup} warm-up steps, the same {steps} fwd+bwd steps the GPU "
-                       f"timed, fp64 oracle (oracle/, OpenMP at the reference's sites, sparse direct solves), mean PD iters "
+                sample=f"rollout 0 of this job from its state after the {args.warmup} warm-up steps, {steps} fwd+bwd steps from the start of "
+                       f"the {args.steps} the GPU timed, fp64 oracle (oracle/, OpenMP at the reference's sites, sparse direct solves), mean PD iters "
                        f"{np.mean([r['iters'] for r in recs]):.0f}, self contacts {np.mean([r['nself'] for r in recs]):.0f}, "
                        + ("direct adjoint solve" if args.adjoint_mode == 1 else "reference adjoint iteration"))
 
@@ -169,13 +174,40 @@ def secondary_config(device, key, K=10):
         return {"workload": key, "error": f"{type(ex).__name__}: {ex}"}
 
 
+# Longest forward + backward sweep of the timed steps. The rollout's cost per step is not stationary: past its first few dozen steps the cloth
+# drapes over and slides down the sphere, and the work of a step grows several fold (100-260 PD iterations and 5 000-7 000 primitive contacts
+# per step by step 80-140, against ~40 and ~300 in the first 20). More --steps therefore run as more sweeps of this length from the same
+# warmed-up state, so that ms_per_step does not depend on --steps and the tape stays W + TIMED_WINDOW steps long.
+TIMED_WINDOW = 20
+
+
+def timed_windows(K):
+    """Lengths of the sweeps the K timed steps run as: a shorter one first if TIMED_WINDOW does not divide K, so the last sweep — the one whose
+    results the caller receives — is always min(K, TIMED_WINDOW) steps long."""
+    T = min(K, TIMED_WINDOW)
+    return [K % T] * (K % T > 0) + [T] * (K // T)
+
+
+def timed_sweep(e, W, K):
+    """The K timed steps: per sweep of n steps, n forward steps from the warmed-up state at slot W, the gradient of the match-trajectory loss
+    (Simulation.cpp:3260-3274: dL/dx = 2 (x - target) / (frames * N)) at its end, n backward steps."""
+    for n in timed_windows(K):
+        e.rollout_forward(W, n); e.seed_gradient(W + n, None, 2.0 / ((n + 1) * e.N)); e.rollout_backward(W + n, n)
+
+
+def timed_slots(W, K):
+    """Tape slot of each of the K timed steps (every sweep rewrites the slots W + 1 ... W + n with the same steps)."""
+    return [W + 1 + s for n in timed_windows(K) for s in range(n)]
+
+
 def c4_share_config(device, args, V, F, V0, flap, center, B=32):
     """The headline workload at the per-GPU share of the 8-GPU job (256 rollouts sharded over 8 ranks = 32 per GPU): the engine splits every rollout over
     8 workgroups (dc_get_cluster) — the figure one GPU can measure of BASELINE.json's "batch 256 sharded over 8 GPUs". Same steps, same settings."""
     try:
         K, W = args.steps, args.warmup
+        n = timed_windows(K)[-1]
         e = make_engine(device, args, V, F, center)
-        e.alloc_batch(B, W + K)
+        e.alloc_batch(B, W + n)
         X0, MU = rollout_inputs(V0, np.arange(B))
         e.set_mu(MU)
         e.set_state(0, X0, np.zeros_like(X0))
@@ -183,17 +215,16 @@ def c4_share_config(device, args, V, F, V0, flap, center, B=32):
             e.set_vertex_forces(np.tile(flap_force(args, e.vertex_data()[0], flap), (B, 1)))
         if W > 0:
             e.rollout_forward(0, W)
-        gscale = 2.0 / ((K + 1) * e.N)
-        e.seed_gradient(W, None, gscale)
+        e.seed_gradient(W, None, 2.0 / ((n + 1) * e.N))
         if W > 0:
             e.rollout_backward(W, 1)
         e.sync(); e.kernel_times(reset=True)
         t0 = time.perf_counter()
-        e.rollout_forward(W, K); e.seed_gradient(W + K, None, gscale); e.rollout_backward(W + K, K)
+        timed_sweep(e, W, K)
         dmu = e.get_mu_gradient().sum(axis=0)
         dt = time.perf_counter() - t0
         kt = e.kernel_times()
-        st = [e.get_stats(s) for s in range(W + 1, W + K + 1)]
+        st = [e.get_stats(s) for s in timed_slots(W, K)]
         pd = float(np.mean([q[0]["pd_iters"].mean() for q in st]))
         out = {"workload": f"C4 (the headline workload) at {B} rollouts: one rank's share of the 8-GPU job, every rollout split over workgroups",
                "rollouts": B, "steps": K, "workgroups_per_rollout": e.cluster(), "rollout_steps_per_s": B * K / dt, "ms_per_batch_step": dt / K * 1e3,
@@ -208,6 +239,30 @@ def c4_share_config(device, args, V, F, V0, flap, center, B=32):
         return out
     except Exception as ex:      # secondary information must never take the headline down
         return {"workload": "C4 at 32 rollouts", "error": f"{type(ex).__name__}: {ex}"}
+
+
+DUMP_BYTES = 64_000_000      # --dump-outputs writes at most this much
+
+
+def dump_sample(B, dofs, small_bytes):
+    """Local rollouts whose state and gradient --dump-outputs writes: all of them when their four float64 arrays (x, v, dL/dx, dL/dv of
+    `dofs` entries each) fit DUMP_BYTES next to the `small_bytes` of the per-rollout dL/dmu, else a fixed, seeded sample of as many as fit."""
+    fit = (DUMP_BYTES - small_bytes - 1024) // (4 * 8 * dofs)      # 1024: the .npy headers
+    if fit < 1:
+        raise SystemExit(f"--dump-outputs: the state and gradient of one rollout ({4 * 8 * dofs} B) exceed {DUMP_BYTES} B")
+    if fit >= B:
+        return np.arange(B)
+    return np.sort(np.random.default_rng(0).choice(B, int(fit), replace=False))
+
+
+def dump_outputs(out_dir, rows, x, v, dx, dv, dmu, dmu_total):
+    """What the timed path hands its caller after its last step, as float64 DIR/<name>.npy: the final state of the sampled rollouts
+    (x, v), the loss gradient with respect to their state at the start of the timed window (dL_dx, dL_dv), dL/dmu of every rollout of
+    this rank (dL_dmu) and its sum over the job (dL_dmu_total)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"x": x[rows], "v": v[rows], "dL_dx": dx[rows], "dL_dv": dv[rows], "dL_dmu": dmu, "dL_dmu_total": np.reshape(dmu_total, -1)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def config_key(args, B, K, W, N):
@@ -261,17 +316,21 @@ def main():
     ap.add_argument("--block-precond", dest="block_precond", type=int, default=0,
                     help="direct adjoint solve preconditioned with K's own 3x3 diagonal blocks (the engine's default, 1.3-1.8 x fewer iterations on "
                          "the garment scenes) or with diag(P) (0). On this soft fabric the blocks buy nothing (37.0 vs 37.4 BiCGSTAB iterations, "
-                         "measured r02r) and cost 8 % per iteration, so the C4 workload runs with 0")
+                         "measured r02r) and cost 8 %% per iteration, so the C4 workload runs with 0")
     ap.add_argument("--selfcollision", type=int, default=1,
                     help="self-collision detection + layered self friction (the reference's default: selfcollisionEnabled = true); 0 = off")
     ap.add_argument("--cluster", type=int, default=-1, help="workgroups per rollout: -1 = engine's choice, 1 = one workgroup per rollout")
     ap.add_argument("--cpu-steps", type=int, default=-1,
-                    help="steps of the CPU baseline sample (rollout 0 from its state after the warm-up steps); -1 = the timed steps, 0 disables")
+                    help="steps of the CPU baseline sample (rollout 0 from its state after the warm-up steps); -1 = the first "
+                         f"min(steps, {CPU_SAMPLE_STEPS}) timed steps, 0 disables")
     ap.add_argument("--tshirt", type=int, default=1, help="also time evaluation 0 of the reference's T-shirt L-BFGS run (secondary line; 0 = skip)")
     ap.add_argument("--secondary", type=str, default="hat,sock,dress,perf_fabric",
                     help="other BASELINE.json configurations in loaded contact states, 10 fwd+bwd steps each (N = 1 only; 'none' = skip)")
     ap.add_argument("--cpu-threads", dest="cpu_threads", type=int, default=0,
                     help="OpenMP threads of the CPU baseline (0: min(host cores, 32), the fastest setting measured on the MI355X host)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what they returned (final state, start-state gradient, dL/dmu) as DIR/<name>.npy in "
+                         "float64 (rank 0; state and gradient of a fixed, seeded sample of the rollouts, at most 64 MB in all)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -309,7 +368,9 @@ def main():
     if args.cluster >= 0:
         os.environ["DC_CLUSTER"] = str(args.cluster)
     e = make_engine(local_rank, args, V, F, center)
-    e.alloc_batch(B, W + K)
+    dump_rows = dump_sample(B, 3 * e.N, 8 * (B + 1) * e.ngroups) if args.dump_outputs and rank == 0 else None
+    n_last = timed_windows(K)[-1]            # the tape holds the warm-up and one sweep
+    e.alloc_batch(B, W + n_last)
     X0, MU = rollout_inputs(V0, ids)
     e.set_mu(MU)
     e.set_state(0, X0, np.zeros_like(X0))
@@ -328,7 +389,7 @@ def main():
     if W > 0:
         e.rollout_forward(0, W)
     # loss gradient of MATCH_TRAJECTORY (Simulation.cpp:3260-3274): dL/dx = 2 (x - target) / (frames * N)
-    gscale = 2.0 / ((K + 1) * e.N)
+    gscale = 2.0 / ((n_last + 1) * e.N)
     e.seed_gradient(W, None, gscale)
     if W > 0:
         e.rollout_backward(W, 1)
@@ -337,9 +398,7 @@ def main():
 
     barrier()
     t0 = time.perf_counter()
-    e.rollout_forward(W, K)                 # K forward steps, tape on the device
-    e.seed_gradient(W + K, None, gscale)    # dL/dx_K of the match-trajectory loss, on the device
-    e.rollout_backward(W + K, K)            # K backward steps
+    timed_sweep(e, W, K)                    # K forward + K backward steps, tape and loss gradient on the device
     # optimiser-level reduction: the friction-coefficient gradient summed over all rollouts of the job — one
     # fused all-reduce (RCCL over xGMI at N > 1, nothing at N = 1), the only exchange between ranks
     dmu_local = e.get_mu_gradient().sum(axis=0)      # also waits for the sweep
@@ -365,7 +424,7 @@ def main():
     pd = cg_f = adj = cg_b = selfc = primc = cyc = it64 = 0.0
     conv = 0
     cg_per_rollout = np.zeros(B); adj_per_rollout = np.zeros(B)       # load balance: a launch lasts as long as its slowest rollout
-    for s in range(W + 1, W + K + 1):
+    for s in timed_slots(W, K):
         fs, bs = e.get_stats(s)
         pd += fs["pd_iters"].sum(); cg_f += fs["cg_iters"].sum(); conv += int((fs["converged"] > 0).sum())
         selfc += fs["self_contacts"].sum(); primc += fs["prim_contacts"].sum()
@@ -466,6 +525,8 @@ def main():
     bound = dom["bound"]
     dx, dv, dmu = e.get_gradient()
     finite = bool(np.isfinite(dx).all() and np.isfinite(dv).all())
+    if dump_rows is not None:
+        dump_outputs(args.dump_outputs, dump_rows, *e.get_state(W + n_last), dx, dv, dmu, dmu_total)
 
     if rank == 0:
         out = {
@@ -507,7 +568,7 @@ def main():
             # dominant kernel first (contract fields), then both kernels
             "roofline": {"bound": bound, **dom, "kernels": [k_fwd, k_bwd]},
         }
-        ncpu = K if args.cpu_steps < 0 else args.cpu_steps
+        ncpu = min(K, CPU_SAMPLE_STEPS) if args.cpu_steps < 0 else args.cpu_steps
         if ncpu > 0:      # rank 0, at every N: the same rollout 0 of the job
             xw, vw = e.get_state(W)
             out["cpu_baseline"] = cpu_baseline(args, V, F, center, field, xw[0], vw[0], MU[0, 0], ncpu, gscale)
