@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = [
     "dc_timer_stop", "dc_kernel_times", "dc_get_cluster", "dc_set_gradient", "dc_set_fixed_point_schedule", "dc_set_force_schedule",
     "dc_set_seed_schedule", "dc_clear_schedules", "dc_get_states", "dc_get_dxfixed", "dc_get_layout", "dc_comm_unique_id", "dc_comm_init", "dc_allreduce_sum", "dc_comm_destroy",
     "dc_get_deflation", "dc_set_record", "dc_set_trajectory_start", "dc_keep_force_gradients", "dc_get_force_gradients", "dc_use_stream", "dc_set_state_dev", "dc_get_state_dev", "dc_step_forward_dev", "dc_step_backward_dev",
+    "dc_get_self_friction_path",
 ]
 
 _lib = None
@@ -482,6 +483,13 @@ class Engine:
         k = C.c_int(); nb = C.c_int()
         self._chk(self.lib.dc_get_cluster(self.h, C.byref(k), C.byref(nb)))
         return k.value
+
+    def self_friction_path(self, reset=False):
+        """[B, 2] per rollout since alloc_batch (or the last reset): PD iterations of the split forward kernel that ran a layered self-friction pass, and
+        those of them in which every part evaluated the layers itself (dc_get_self_friction_path); zeros with one workgroup per rollout"""
+        out = np.zeros((self.B, 2), dtype=np.int32)
+        self._chk(self.lib.dc_get_self_friction_path(self.h, _i(out), C.c_int(int(reset))))
+        return out
 
     def timer_start(self):
         self._chk(self.lib.dc_timer_start(self.h))

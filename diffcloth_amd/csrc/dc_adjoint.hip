@@ -895,7 +895,7 @@ __global__ __launch_bounds__(THREADS) void k_adjoint_step(const DevSystem *__res
     // (meshes the engine found ill-conditioned: where the fp64 fall-back of THIS instance has the coarse level — the condition of
     // bicgstab64, dc_adjoint64.h — the fp32 solve hands over after 400 iterations; everywhere else it keeps its budget, the fall-back
     // there is block-Jacobi only and much slower per digit: ADVICE r04)
-    const bool fb_coarse = COARSE && S.defl_u != nullptr && S.adj_coarse && C.lds_floats >= kCoarseLdsFloats;
+    const bool fb_coarse = !A.fp32_only && COARSE && S.defl_u != nullptr && S.adj_coarse && C.lds_floats >= kCoarseLdsFloats;      // (fp32_only: no fall-back to hand over to)
     const int kcap = std::min(A.it_cap > 0 ? 4 * A.it_cap : 1600, fb_coarse ? 400 : 1 << 30);
     // true residual of the start: g itself for u = 0 (mode 1), g - K u after the reference iteration hit its cap (mode 0);
     // `gin` holds the right-hand side of the next fp32 solve: g, later the fp64 residual rounded to fp32
@@ -908,7 +908,8 @@ __global__ __launch_bounds__(THREADS) void k_adjoint_step(const DevSystem *__res
     double rr = rr_true;
     double op_err = 0;         // measured error of the fp32 operator (see below)
     bool fallback = false;
-    bool use_cg = !BLK && !COARSE && A.cg_first != 0;      // CG first; BiCGSTAB once a CG cycle has not contracted the fp64 residual (cg32_solve)
+    bool use_cg = !BLK && !COARSE && A.cg_first != 0 && !A.fp32_only;      // CG first; BiCGSTAB once a CG cycle has not contracted the fp64 residual (cg32_solve)
+    // (not with fp32_only: that mode is ONE solve, with nothing after it to take over from a CG cycle on its short leash — BiCGSTAB alone, to kcap)
     status = (rr_true <= stop) ? 1 : 0;
     for (int kdone = 0; status == 0 && !fallback; cycles++) {
     // inner tolerance of this cycle: what is left to the target, but never below kInnerFloor of the cycle's own right-hand side

@@ -280,13 +280,14 @@ __global__ __launch_bounds__(THREADS) void k_adjoint_step_cl(const DevSystem *__
     // (meshes the engine found ill-conditioned: where the fp64 fall-back of THIS instance has the coarse level — the condition of
     // bicgstab64, dc_adjoint64.h — the fp32 solve hands over after 400 iterations; everywhere else it keeps its budget, the fall-back
     // there is block-Jacobi only and much slower per digit: ADVICE r04)
-    const bool fb_coarse = COARSE && S.defl_u != nullptr && S.adj_coarse && hc_off >= kCoarseLdsFloats;
+    const bool fb_coarse = !A.fp32_only && COARSE && S.defl_u != nullptr && S.adj_coarse && hc_off >= kCoarseLdsFloats;      // (fp32_only: no fall-back to hand over to)
     const int kcap = std::min(A.it_cap > 0 ? 4 * A.it_cap : 1600, fb_coarse ? 400 : 1 << 30);
     constexpr int VB = 4;
     bool fallback = false;
     double rr = rr_true;
     double op_err = 0;         // measured error of the fp32 operator (see below)
-    bool use_cg = !BLK && !COARSE && A.cg_first != 0;      // correction solves by CG first, BiCGSTAB once a CG cycle has not delivered (dc_adjoint.hip: cg32_solve)
+    bool use_cg = !BLK && !COARSE && A.cg_first != 0 && !A.fp32_only;      // correction solves by CG first, BiCGSTAB once a CG cycle has not delivered (dc_adjoint.hip: cg32_solve)
+    // (not with fp32_only: that mode is ONE solve, with nothing after it to take over from a CG cycle on its short leash — BiCGSTAB alone, to kcap)
     status = (rr_true <= stop) ? 1 : 0;
     for (int kdone = 0; status == 0 && !fallback; cycles++) {
     const double rel_now = sqrt(rr_true) / gnorm;

@@ -53,6 +53,8 @@ struct DevCluster {
   long long spin_limit;        // bound of every spin in ticks of the 100 MHz wall clock (kSpinLimit; tests shorten it: DC_TEST_SPIN_MS)
   int redundant_self;          // forward: every part evaluates the layered self friction itself when the rollout's parts share an XCD (DC_SELF_REDUNDANT=0: part 0 alone, rounds 2-5)
   int test_drop;               // test hook (DC_TEST_DROP_PART=1): the last part of the launch's first rollout leaves at once — its peers must time out cleanly
+  int test_skew;               // test hook (DC_TEST_SKEW_PART=p): part p of every rollout starts the forward's layered self friction 30 us late (-1: off)
+  int *self_path;              // [B][2] forward PD iterations with a layered self-friction pass, and those of them that ran it in every part (dc_get_self_friction_path)
   const DevCluster *self_dev;
 };
 

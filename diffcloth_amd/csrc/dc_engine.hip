@@ -342,10 +342,11 @@ int build_cluster(dc_ctx *c, int K, bool forced) {
   DevCluster &D = cl.D;
   std::memset(&D, 0, sizeof(D));
   D.K = K; D.R = R; D.HB = HB; D.wpp = wpp; D.xch_stride = kXchWaves + 2 * HB; D.pk_vpt = vpt;
-  D.spin_limit = kSpinLimit; D.test_drop = 0;
+  D.spin_limit = kSpinLimit; D.test_drop = 0; D.test_skew = -1;
   { const char *ev = getenv("DC_SELF_REDUNDANT"); D.redundant_self = ev ? (ev[0] == '1') : 1; }
   if (const char *ev = getenv("DC_TEST_SPIN_MS")) { const long long ms = atoll(ev); if (ms > 0) D.spin_limit = ms * 100000ll; }      // test hooks
   if (const char *ev = getenv("DC_TEST_DROP_PART")) D.test_drop = ev[0] == '1';
+  if (const char *ev = getenv("DC_TEST_SKEW_PART")) D.test_skew = atoi(ev);
   int rc;
   const int *ip; const float *fp;
   if ((rc = upload_cl<int>(c, &ip, HW.win))) return rc;
@@ -381,6 +382,7 @@ int build_cluster(dc_ctx *c, int K, bool forced) {
   cl.xch_bytes = (size_t) cl.nb * K * 2 * D.xch_stride * sizeof(v4i);
   if ((rc = dev_alloc(c, cl.allocs, &D.xch, cl.xch_bytes / sizeof(v4i)))) return rc;
   if ((rc = dev_alloc(c, cl.allocs, &D.err, 4))) return rc;
+  if ((rc = dev_alloc(c, cl.allocs, &D.self_path, 2 * (size_t) c->B))) return rc;
   DevCluster *dD = nullptr;
   if ((rc = dev_alloc(c, cl.allocs, &dD, 1))) return rc;
   D.self_dev = dD;
@@ -1812,6 +1814,16 @@ int dc_get_cluster(const dc_ctx *c, int *workgroups_per_rollout, int *rollouts_p
   if (!c) return DC_ERR_INVALID;
   if (workgroups_per_rollout) *workgroups_per_rollout = c->cl.ok ? c->cl.K : 1;
   if (rollouts_per_launch) *rollouts_per_launch = c->cl.ok ? c->cl.nb : c->B;
+  return DC_OK;
+}
+
+int dc_get_self_friction_path(dc_ctx *c, int *out, int reset) {
+  if (!c || !out) return DC_ERR_INVALID;
+  std::memset(out, 0, sizeof(int) * 2 * (size_t) std::max(c->B, 0));
+  if (!c->cl.ok || c->B <= 0) return DC_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, c->cl.D.self_path, sizeof(int) * 2 * (size_t) c->B, hipMemcpyDeviceToHost));
+  if (reset) HIPCHK(c, hipMemsetAsync(c->cl.D.self_path, 0, sizeof(int) * 2 * (size_t) c->B, c->stream));
   return DC_OK;
 }
 

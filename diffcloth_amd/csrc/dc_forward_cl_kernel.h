@@ -25,18 +25,20 @@ namespace dc {
 // of the contacts (f, r of its ~2 x nself vertices through the sc1 path, the contact lists of part 0's detection through Sc1Table), walks the
 // layers in its own LDS — identical inputs, identical arithmetic, identical results in every part — and then writes r and re-forms the right-hand
 // side for ITS OWN rows of the working set only. Before: part 0 alone ran the layers between two cross-part barriers and every part re-formed the
-// right-hand side of all its rows from global memory afterwards; the second barrier and that pass are gone. Returns false (nothing done) when the
-// working set does not fit the LDS offered — a function of values every part reads identically, so all parts take the same branch.
+// right-hand side of all its rows from global memory afterwards; that pass is gone. The r a part stages is the r its peers overwrite with
+// the post-friction values of their rows, so no part may write before every part has staged: a split exchange (arrive once staged, wait before
+// the write-back) orders the two and overlaps its latency with the layers. Returns 0 (nothing done) when the working set does not fit the LDS
+// offered — a function of values every part reads identically, so all parts take the same branch — 1 when done, -1 when the exchange timed out.
 // Only called when Xch::same_xcd holds (dc_cluster.h: Sc1Table). Same LDS layout and contact code as self_friction_layers_lds_v (dc_devlib.h).
 template <int THREADS, class FV, class RV, class RHS>
-__device__ __forceinline__ bool self_friction_layers_parts(const DevSystem &S, const SelfRec &R, int b, const FV &f, const RV &r, float *lds, int lds_floats,
-                                                           int r0, int r1, bool write_d, RHS rhs_of) {
+__device__ __forceinline__ int self_friction_layers_parts(const DevSystem &S, const SelfRec &R, int b, const FV &f, const RV &r, float *lds, int lds_floats,
+                                                          int r0, int r1, bool write_d, Xch &X, RHS rhs_of) {
   const int cap = S.self_cap, N = S.N, tid = threadIdx.x;
   const Sc1Table meta = sc1_table(R.meta + (size_t) b * kMetaStride, sizeof(int) * (size_t) kMetaStride);
   const Sc1Table nrm = sc1_table(R.nrm + (size_t) b * cap, sizeof(float4) * (size_t) cap);
   const Sc1Table verts = sc1_table(R.verts + (size_t) b * 2 * cap, sizeof(int) * 2 * (size_t) cap);
   const int C = min(meta.ldi(0), cap), nl = meta.ldi(1), M = meta.ldi(kMetaStride - 1);
-  if (!S.self_lds || self_lds_need(M, C, nl) > lds_floats || nl + 2 >= kMetaStride - 4) return false;
+  if (!S.self_lds || self_lds_need(M, C, nl) > lds_floats || nl + 2 >= kMetaStride - 4) return 0;
   float4 *dvec = R.dvec + (size_t) b * cap;
   float *lf = lds, *lr = lds + 3 * M, *lim = lds + 6 * M;
   float4 *ln = (float4 *) (lds + 7 * M + ((4 - (7 * M) % 4) % 4));       // 16-byte aligned
@@ -50,7 +52,9 @@ __device__ __forceinline__ bool self_friction_layers_parts(const DevSystem &S, c
   }
   for (int k = tid; k < C; k += THREADS) ln[k] = nrm.ld4(k);
   for (int l = tid; l <= nl; l += THREADS) loff[l] = meta.ldi(2 + l);
-  __syncthreads();
+  __syncthreads();                          // (every wave's staging loads have returned: their values are in LDS)
+  xch_begin(X);
+  xch_publish_sums(X, 0.f, 0.f, 0.f);       // arrive: this part has staged
   auto contact = [&](int k) {
     const float4 n4 = ln[k];
     const int sl = __float_as_int(n4.w), sa = sl & 0xffff, sb = sl >> 16;
@@ -80,6 +84,11 @@ __device__ __forceinline__ bool self_friction_layers_parts(const DevSystem &S, c
     }
     __syncthreads();
   }
+  {   // wait: every part has staged, r of the working set may change
+    double z[3];
+    f3 none[1];
+    if (!xch_finish<THREADS, 1, false>(X, z, none)) return -1;
+  }
   for (int s = tid; s < M; s += THREADS) {
     const int v = verts.ldi(s);
     if (v >= r0 && v < r1) {
@@ -90,7 +99,7 @@ __device__ __forceinline__ bool self_friction_layers_parts(const DevSystem &S, c
   }
   if (write_d) for (int k = tid; k < C; k += THREADS) dvec[k] = ld[k];
   __syncthreads();
-  return true;
+  return 1;
 }
 
 // PIPE: the inner solve is the single-exchange CG (one exchange per iteration instead of two), see the loop
@@ -241,11 +250,21 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_cl(const DevSystem *__restr
     X.site = 4;
     if (nself > 0) {   // layered self friction (Simulation.cpp:655-678) over the rollout's f / r, then the right-hand side of the vertices it touched
       if (!xch_barrier<THREADS>(X)) return;
-      bool redundant = false;
-      if (X.same_xcd && redundant_layers)      // every part for itself (self_friction_layers_parts above): no second barrier, no pass over all rows
-        redundant = self_friction_layers_parts<THREADS>(S, srec, b, rfb, rrb, lds, fric_floats, r0, r1, part == 0, [&](int i, f3 fv, f3 rv) {
+      if (part == CL.test_skew) {              // test hook (DC_TEST_SKEW_PART): this part starts the pass 30 us late, far below the spin bound
+        const long long t0 = (long long) __builtin_amdgcn_s_memrealtime();
+        while ((long long) __builtin_amdgcn_s_memrealtime() - t0 < 3000) __builtin_amdgcn_s_sleep(8);
+      }
+      int redundant = 0;
+      if (X.same_xcd && redundant_layers) {    // every part for itself (self_friction_layers_parts above): no pass over all rows
+        redundant = self_friction_layers_parts<THREADS>(S, srec, b, rfb, rrb, lds, fric_floats, r0, r1, part == 0, X, [&](int i, f3 fv, f3 rv) {
           st3(scr, i, N, (fv + rv - ld3c(vnb, i) * S.mass[i]) * CL.sq_dinv[i]);
         });
+        if (redundant < 0) return;
+      }
+      if (tid == 0 && part == 0 && CL.self_path) {      // which path ran (dc_get_self_friction_path)
+        atomicAdd(CL.self_path + 2 * b, 1);
+        if (redundant) atomicAdd(CL.self_path + 2 * b + 1, 1);
+      }
       if (!redundant) {
         if (part == 0) {
           if (!self_friction_layers_lds_v<THREADS>(S, srec, b, rfb, rrb, lds, fric_floats)) self_friction_layers_v<THREADS>(S, srec, b, rfb, rrb);

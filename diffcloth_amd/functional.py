@@ -57,17 +57,20 @@ class BatchedSim:
         import warnings
         e = self.engine
         e.sync()                                     # raises on a timed-out exchange
-        bad_pairs, worst, first = 0, 0.0, None
+        bad_pairs, worst, first, worst_at = 0, -1.0, None, None
         for slot in range(1, self.step_idx + 1):
             fwd, bwd = e.get_stats(slot)             # raises DC_ERR_CAPACITY on a self-contact overflow of that step
             if slot in self._bwd_slots and (bwd["converged"] == 0).any():
                 bad = np.nonzero(bwd["converged"] == 0)[0]
                 bad_pairs += len(bad)
-                w = int(bad[np.argmax(bwd["last_udiff"][bad])])
+                # a non-finite residual (a diverged solve) is the worst there is
+                res = np.asarray(bwd["last_udiff"], dtype=np.float64)[bad]
+                res = np.where(np.isfinite(res), res, np.inf)
+                w = int(bad[np.argmax(res)])
                 if first is None:
                     first = (slot, int(bad[0]))
-                if float(bwd["last_udiff"][w]) >= worst:
-                    worst, worst_at = float(bwd["last_udiff"][w]), (slot, w)
+                if worst_at is None or res.max() > worst:
+                    worst, worst_at = float(res.max()), (slot, w)
         self.unconverged = bad_pairs                 # (step, rollout) pairs of the episode whose adjoint solve did not converge
         if bad_pairs:
             msg = (f"BatchedSim: {bad_pairs} adjoint solve(s) of this episode did not converge (first: step {first[0]}, rollout {first[1]}; "

@@ -89,7 +89,9 @@ typedef struct dc_params {
    * in fp64 from fp64 rest-shape tables, until |g - K u| <= adjoint_rel_tol |g| holds in fp64; when the fp32 solve makes no
    * progress (adjoint systems beyond fp32, e.g. a compressed fine garment) a block-Jacobi BiCGSTAB in fp64 on the same operator
    * takes over — the role of the reference's fp64 SparseLU (Simulation.cpp:1431-1440), which always returns a solution.
-   * 1 = the fp32 Krylov solve alone (round-2 behaviour: gradients at eps_fp32 * cond(K), 1-3e-4 on stiff / large scenes).   */
+   * 1 = one fp32 BiCGSTAB solve alone, never CG, for up to 4 x adjoint_iter_cap iterations with no early hand-over (round-2 behaviour:
+   * gradients at eps_fp32 * cond(K), 1-3e-4 on stiff / large scenes; systems beyond fp32 end unconverged after that budget;
+   * dc_bwd_stats: fp64_iters = residual_verified = 0, last_udiff = the recurrence residual, and with adjoint_mode 1 cg_iters = 0).   */
   int adjoint_fp32_only;
   int max_self_contacts;            /* capacity of the per-rollout self-contact list of one step; <=0: sized from the mesh,
                                        max(2048, N) pairs (at most 16000); overflow is reported, never silent: dc_step_stats */
@@ -327,6 +329,11 @@ int dc_sync(dc_ctx *ctx);
  * and the device (environment DC_CLUSTER=k forces k; 0 or 1 = one workgroup per rollout). Results agree with the one-workgroup
  * kernels to solver tolerance (different summation order), not bitwise. Reports K and how many rollouts one launch covers. */
 int dc_get_cluster(const dc_ctx *ctx, int *workgroups_per_rollout, int *rollouts_per_launch);
+/* Which path the split forward kernel took for the layered self friction (Simulation.cpp:655-678), counted per rollout since dc_alloc_batch
+ * (or the last reset): out[2 b] = PD iterations that ran a self-friction pass, out[2 b + 1] = those of them in which every part evaluated the
+ * layers itself (the parts share an XCD and the working set fits the LDS; DC_SELF_REDUNDANT=0 turns it off) instead of part 0 alone. All zero
+ * when the batch runs one workgroup per rollout. Synchronises; reset != 0 zeroes the counters afterwards.                                    */
+int dc_get_self_friction_path(dc_ctx *ctx, int *out /*B*2*/, int reset);
 /* Which kernel set dc_build chose for this system (works on a host-only context too): out6 = {vertices renumbered on the device
  * (0 / 1), bandwidth of the system matrix in device numbering, packet-matrix forward kernel usable (needs bandwidth <= 511),
  * LDS element windows usable, number of element windows, explicit-inverse solve (small meshes)}. A mesh that fails the packet /
