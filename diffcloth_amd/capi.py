@@ -61,7 +61,7 @@ EXPORTED_SYMBOLS = [
     "dc_timer_stop", "dc_kernel_times", "dc_get_cluster", "dc_set_gradient", "dc_set_fixed_point_schedule", "dc_set_force_schedule",
     "dc_set_seed_schedule", "dc_clear_schedules", "dc_get_states", "dc_get_dxfixed", "dc_get_layout", "dc_comm_unique_id", "dc_comm_init", "dc_allreduce_sum", "dc_comm_destroy",
     "dc_get_deflation", "dc_set_record", "dc_set_trajectory_start", "dc_keep_force_gradients", "dc_get_force_gradients", "dc_use_stream", "dc_set_state_dev", "dc_get_state_dev", "dc_step_forward_dev", "dc_step_backward_dev",
-    "dc_get_self_friction_path",
+    "dc_get_self_friction_path", "dc_get_adjoint_matrix", "dc_dense_phase_times",
 ]
 
 _lib = None
@@ -164,9 +164,10 @@ class Engine:
         if backward_tol is not None: p.backward_tol = backward_tol
         if gradient_clipping is not None: p.gradient_clipping = int(gradient_clipping)
         if clip_threshold is not None: p.gradient_clipping_threshold = clip_threshold
-        if force_direct_adjoint is not None: p.adjoint_mode = 1 if force_direct_adjoint else 0
+        # a direct solve asked for keeps the dense one (adjoint_mode 2), as dc_set_solver does
+        if force_direct_adjoint is not None: p.adjoint_mode = (2 if p.adjoint_mode == 2 else 1) if force_direct_adjoint else 0
         self._chk(self.lib.dc_set_solver(self.h, C.c_double(p.forward_tol), C.c_double(p.backward_tol), C.c_int(p.gradient_clipping),
-                                         C.c_double(p.gradient_clipping_threshold), C.c_int(int(p.adjoint_mode == 1))))
+                                         C.c_double(p.gradient_clipping_threshold), C.c_int(int(p.adjoint_mode in (1, 2)))))
 
     def set_primitives(self, prims):
         """prims: list of dicts(kind, group, center, top_offset, radius, length, mu, rotates)."""
@@ -498,6 +499,20 @@ class Engine:
         ms = C.c_float()
         self._chk(self.lib.dc_timer_stop(self.h, C.byref(ms)))
         return ms.value
+
+    def adjoint_matrix(self, slot, rollout):
+        """K = P - dP^T of record `slot`, rollout `rollout`, as the dense adjoint solve assembles it (dc_get_adjoint_matrix): (3N, 3N) float64,
+        xyz interleaved in the caller's numbering"""
+        n = 3 * self.N
+        K = np.zeros((n, n))
+        self._chk(self.lib.dc_get_adjoint_matrix(self.h, C.c_int(slot), C.c_int(rollout), _d(K)))
+        return K
+
+    def dense_phase_times(self, reset=False):
+        """device ms of the mode-2 backward steps: (assembly, factorisation, solve); only with DC_DENSE_TIMES=1 (dc_dense_phase_times)"""
+        ms = (C.c_float * 3)()
+        self._chk(self.lib.dc_dense_phase_times(self.h, ms, C.c_int(int(reset))))
+        return tuple(float(v) for v in ms)
 
     def kernel_times(self, reset=False):
         a = C.c_float(); b = C.c_float(); na = C.c_int(); nb = C.c_int()

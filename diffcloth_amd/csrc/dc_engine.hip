@@ -27,6 +27,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "dc_spheremesh.h"
 #include "dc_selftmp.h"
 #include "dc_cluster.h"
+#include "dc_adjoint_dense.h"
 
 using namespace dc;
 
@@ -116,6 +117,14 @@ struct dc_ctx {
   HostDeflation defl_cache;
   uint64_t defl_key = 0;
   bool defl_cache_valid = false, defl_cache_built = false;
+  // dense direct adjoint solve (adjoint_mode 2, dc_adjoint_dense.h): matrices / factors of a chunk of dense_nb rollouts, allocated in the
+  // batch pool on the first mode-2 backward step; phase times (assembly, factorisation, solve) when DC_DENSE_TIMES=1
+  DenseAdjWork dense{};
+  int dense_nb = 0;
+  int dense_launches = 0;           // kernel launches of the mode-2 backward steps enqueued (counter; dc_rollout_backward adds the difference)
+  bool dense_timing = false;
+  float dense_ms[3] = {0, 0, 0};
+  hipEvent_t ev_d[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 namespace {
@@ -467,6 +476,72 @@ int cluster_check(dc_ctx *c) {       // after a synchronisation
 bool use_cluster_fwd(const dc_ctx *c) { return c->cl.ok; }
 bool use_cluster_bwd(const dc_ctx *c) { return c->cl.ok && c->params.adjoint_mode == 1; }
 
+// adjoint_mode 2 needs the whole K of a rollout as a dense matrix: meshes of at most kDenseMaxN vertices
+int check_dense_mode(dc_ctx *c, int mode, int N, const char *who) {
+  if (mode == 2 && N > kDenseMaxN)
+    return fail(c, DC_ERR_INVALID, std::string(who) + ": adjoint_mode 2 (dense direct adjoint solve) is limited to meshes of at most " +
+                std::to_string(kDenseMaxN) + " vertices; this mesh has " + std::to_string(N));
+  return DC_OK;
+}
+
+// Scratch of the dense adjoint solve, on first use: as many rollouts per chunk as fit a budget of 8 GB (DC_DENSE_CHUNK=k caps the chunk at
+// k rollouts, development switch: the chunked path on small batches)
+int dense_ensure(dc_ctx *c) {
+  if (c->dense.K) return DC_OK;
+  const int N = c->host.N, ld = dense_adj_ld(N), cap = std::max(c->self_cap, 1);
+  const size_t per = (size_t) ld * ld * sizeof(double) + (size_t) ld * sizeof(int) + sizeof(int) + (size_t) 9 * N * sizeof(double) +
+                     (size_t) 9 * cap * sizeof(double);
+  const size_t budget = (size_t) 8 << 30;
+  int nb = (int) std::max<size_t>(1, std::min<size_t>((size_t) c->B, budget / per));
+  const char *env = getenv("DC_DENSE_CHUNK");
+  if (env && atoi(env) > 0) nb = std::min(nb, atoi(env));
+  int rc;
+  DenseAdjWork &D = c->dense;
+  D.ld = ld;
+  if ((rc = dev_alloc(c, c->batch_allocs, &D.K, (size_t) nb * ld * ld))) return rc;
+  if ((rc = dev_alloc(c, c->batch_allocs, &D.piv, (size_t) nb * ld))) return rc;
+  if ((rc = dev_alloc(c, c->batch_allocs, &D.flag, (size_t) nb))) return rc;
+  if ((rc = dev_alloc(c, c->batch_allocs, &D.pm, (size_t) nb * 9 * N))) return rc;
+  if ((rc = dev_alloc(c, c->batch_allocs, &D.sg, (size_t) nb * 9 * cap))) return rc;
+  c->dense_nb = nb;
+  const char *envt = getenv("DC_DENSE_TIMES");
+  c->dense_timing = envt && envt[0] == '1';
+  if (c->dense_timing)
+    for (auto &e : c->ev_d) if (!e) HIPCHK(c, hipEventCreate(&e));
+  return DC_OK;
+}
+
+// one mode-2 backward step (A.nsteps == 1): per chunk of rollouts assemble K -> factor -> adjoint step with the factors
+int enqueue_dense_adjoint(dc_ctx *c, const BwdArgs &A) {
+  if (A.nsteps != 1) return fail(c, DC_ERR_INVALID, "adjoint_mode 2 runs one backward step per launch");
+  int rc;
+  if ((rc = dense_ensure(c))) return rc;
+  const DenseAdjWork &D = c->dense;
+  const int n = 3 * c->host.N;
+  for (int b0 = 0; b0 < c->B; b0 += c->dense_nb) {
+    const int nb = std::min(c->dense_nb, c->B - b0);
+    if (c->dense_timing) HIPCHK(c, hipEventRecord(c->ev_d[0], c->stream));
+    HIPCHK(c, hipMemsetAsync(D.flag, 0, sizeof(int) * nb, c->stream));
+    launch_dense_assemble(c->S, A, c->W.x64, D, b0, nb, c->stream);
+    if (c->dense_timing) HIPCHK(c, hipEventRecord(c->ev_d[1], c->stream));
+    c->dense_launches += 2 + launch_dense_factor(D, n, nb, c->stream);
+    if (c->dense_timing) HIPCHK(c, hipEventRecord(c->ev_d[2], c->stream));
+    launch_dense_adjoint_step(c->S, c->W, A, D, b0, nb, c->stream);
+    c->dense_launches += 1;
+    HIPCHK(c, hipGetLastError());
+    if (c->dense_timing) {
+      HIPCHK(c, hipEventRecord(c->ev_d[3], c->stream));
+      HIPCHK(c, hipEventSynchronize(c->ev_d[3]));
+      for (int k = 0; k < 3; k++) {
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev_d[k], c->ev_d[k + 1]));
+        c->dense_ms[k] += ms;
+      }
+    }
+  }
+  return DC_OK;
+}
+
 int enqueue_pd_step(dc_ctx *c, const FwdArgs &A) {
   {   // a forward step overwrites records: a record handed in from outside for one of them (dc_set_record) is gone
     const long first = (long) ((A.x_out - c->X) / (long) slot_elems(c));
@@ -480,6 +555,7 @@ int enqueue_pd_step(dc_ctx *c, const FwdArgs &A) {
   return DC_OK;
 }
 int enqueue_adjoint_step(dc_ctx *c, const BwdArgs &A) {
+  if (c->params.adjoint_mode == 2) return enqueue_dense_adjoint(c, A);
   if (!use_cluster_bwd(c)) { launch_adjoint_step(c->S, c->W, A, c->B, c->stream); HIPCHK(c, hipGetLastError()); return DC_OK; }
   for (int b0 = 0; b0 < c->B; b0 += c->cl.nb) {
     HIPCHK(c, hipMemsetAsync(c->cl.D.xch, 0, c->cl.xch_bytes, c->stream));
@@ -547,6 +623,7 @@ int dc_destroy(dc_ctx *c) {
   free_pool(c->batch_allocs);
   (void) hipEventDestroy(c->ev_a); (void) hipEventDestroy(c->ev_b);
   (void) hipEventDestroy(c->ev_t0); (void) hipEventDestroy(c->ev_t1);
+  for (hipEvent_t e : c->ev_d) if (e) (void) hipEventDestroy(e);
   (void) hipStreamDestroy(c->own_stream);
   delete c;
   return DC_OK;
@@ -591,6 +668,7 @@ int dc_set_attachments(dc_ctx *c, int count, const int *vertex) {
 int dc_set_params(dc_ctx *c, const dc_params *p) {
   if (!c || !p) return DC_ERR_INVALID;
   if (!(p->time_step > 0) || !(p->density > 0)) return fail(c, DC_ERR_INVALID, "dc_set_params: time_step and density must be > 0");
+  if (c->mesh_set) { const int rc = check_dense_mode(c, p->adjoint_mode, c->host.N, "dc_set_params"); if (rc) return rc; }
   c->params = *p;
   c->built = false;
   return DC_OK;
@@ -626,6 +704,7 @@ int dc_set_primitives(dc_ctx *c, int count, const dc_primitive *prims) {
 int dc_build(dc_ctx *c) {
   if (!c) return DC_ERR_INVALID;
   if (!c->mesh_set) return fail(c, DC_ERR_STATE, "dc_build: dc_set_mesh has not been called");
+  { const int rc = check_dense_mode(c, c->params.adjoint_mode, c->host.N, "dc_build"); if (rc) return rc; }
   c->inj_slot = -1;      // a rebuilt system no longer matches a record handed in before (dc_set_record)
   const dc_params &p = c->params;
   HostSystem &H = c->host;
@@ -833,7 +912,7 @@ int dc_build(dc_ctx *c) {
   {  // small meshes: explicit inverse of the scaled matrix (dc_dense.h) for the forward global step
     HostDense HD;
     const char *envd = getenv("DC_DENSE_MAX_N");   // development switch: 0 disables, other values move the size limit
-    const int max_n = envd ? atoi(envd) : 768;          // 2.4 MB: the matrix must stay in every XCD's 4 MB L2 next to the other tables
+    const int max_n = envd ? atoi(envd) : kDenseMaxN;   // 2.4 MB: the matrix must stay in every XCD's 4 MB L2 next to the other tables
     S.dense_inv = nullptr; S.dense_ld = 0;
     if (S.pk_ok && S.win_ok && HD.build(H, max_n)) {
       if ((rc = upload<float>(c, &S.dense_inv, HD.inv))) return rc;
@@ -884,7 +963,8 @@ int dc_set_solver(dc_ctx *c, double forward_tol, double backward_tol, int gradie
   if (!c) return DC_ERR_INVALID;
   c->params.forward_tol = forward_tol; c->params.backward_tol = backward_tol;
   c->params.gradient_clipping = gradient_clipping; c->params.gradient_clipping_threshold = clip_threshold;
-  c->params.adjoint_mode = force_direct_adjoint ? 1 : 0;
+  // a direct solve is asked for: the dense one (mode 2) is one, so it stays; otherwise the Krylov direct solve (mode 1)
+  c->params.adjoint_mode = force_direct_adjoint ? (c->params.adjoint_mode == 2 ? 2 : 1) : 0;
   return DC_OK;   // solver knobs are kernel arguments: no rebuild, the batch and its tape stay valid
 }
 
@@ -952,6 +1032,7 @@ int dc_alloc_batch(dc_ctx *c, int B, int tape) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   free_pool(c->batch_allocs);
+  c->dense = DenseAdjWork{}; c->dense_nb = 0;
   c->B = B; c->tape = tape; c->start_slot = 0;
   const int N = c->host.N, Af = (int) c->host.att_vertex.size(), NC = c->S.NC, G = c->S.ngroups;
   const size_t se = (size_t) B * 3 * N, slots = (size_t) tape + 1;
@@ -1521,7 +1602,8 @@ int dc_rollout_backward(dc_ctx *c, int slot, int nsteps) {
   }
   if (c->S.Af > 0) HIPCHK(c, hipMemsetAsync(c->DXF + (size_t) c->B * 3 * c->S.Af * (slot - nsteps + 1), 0, sizeof(float) * c->B * 3 * c->S.Af * nsteps, c->stream));
   const bool inj_inside = c->inj_slot >= slot - nsteps + 1 && c->inj_slot <= slot;      // (dc_set_record: that step gets a launch of its own)
-  const bool fused_bwd = fuse_ok && nsteps > 1 && !inj_inside;
+  const bool fused_bwd = fuse_ok && nsteps > 1 && !inj_inside && c->params.adjoint_mode != 2;     // (mode 2: assemble -> factor -> step per step)
+  const int dense_before = c->dense_launches;
   if (fused_bwd) {
     BwdArgs A = bwd_args(c, slot, slot == c->start_slot + 1, false);
     A.nsteps = nsteps;                       // the whole sweep of a rollout in one launch
@@ -1538,7 +1620,7 @@ int dc_rollout_backward(dc_ctx *c, int slot, int nsteps) {
   float ms = 0;
   HIPCHK(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
   const int chunks = use_cluster_bwd(c) ? (c->B + c->cl.nb - 1) / c->cl.nb : 1;
-  c->bwd_ms += ms; c->bwd_launches += (fused_bwd ? 1 : nsteps) * chunks;
+  c->bwd_ms += ms; c->bwd_launches += c->params.adjoint_mode == 2 ? c->dense_launches - dense_before : (fused_bwd ? 1 : nsteps) * chunks;
   return cluster_check(c);
 }
 
@@ -1839,6 +1921,41 @@ int dc_timer_stop(dc_ctx *c, float *ms) {
   HIPCHK(c, hipEventElapsedTime(ms, c->ev_t0, c->ev_t1));
   return DC_OK;
 }
+int dc_get_adjoint_matrix(dc_ctx *c, int slot, int rollout, double *K) {
+  int rc = check_batch(c, slot, slot);
+  if (rc) return rc;
+  if (slot < 1 || rollout < 0 || rollout >= c->B || !K) return fail(c, DC_ERR_INVALID, "dc_get_adjoint_matrix: bad slot / rollout / output");
+  const int N = c->host.N, n = 3 * N;
+  if ((rc = check_dense_mode(c, 2, N, "dc_get_adjoint_matrix"))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = dense_ensure(c))) return rc;
+  const DenseAdjWork &D = c->dense;
+  launch_dense_assemble(c->S, bwd_args(c, slot, false, false), c->W.x64, D, rollout, 1, c->stream);
+  HIPCHK(c, hipGetLastError());
+  std::vector<double> Kd((size_t) D.ld * n);
+  HIPCHK(c, hipMemcpyAsync(Kd.data(), D.K, Kd.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  // device (planar, renumbered, column-major) -> the caller's (xyz interleaved, caller's numbering, row-major)
+  for (int cj = 0; cj < 3; cj++)
+    for (int j = 0; j < N; j++) {
+      const int uj = c->user_of.empty() ? j : c->user_of[j];
+      const double *col = Kd.data() + (size_t) (cj * N + j) * D.ld;
+      for (int ci = 0; ci < 3; ci++)
+        for (int i = 0; i < N; i++) {
+          const int ui = c->user_of.empty() ? i : c->user_of[i];
+          K[(size_t) (3 * ui + ci) * n + 3 * uj + cj] = col[ci * N + i];
+        }
+    }
+  return DC_OK;
+}
+
+int dc_dense_phase_times(dc_ctx *c, float *ms3, int reset) {
+  if (!c || !ms3) return DC_ERR_INVALID;
+  for (int k = 0; k < 3; k++) ms3[k] = c->dense_ms[k];
+  if (reset) for (float &v : c->dense_ms) v = 0;
+  return DC_OK;
+}
+
 int dc_kernel_times(dc_ctx *c, float *fwd_ms, int *fwd_launches, float *bwd_ms, int *bwd_launches, int reset) {
   if (!c) return DC_ERR_INVALID;
   if (fwd_ms) *fwd_ms = c->fwd_ms;

@@ -78,7 +78,12 @@ typedef struct dc_params {
   /* adjoint solver: 0 = the reference's fixed-point iteration u <- P^-1 (g + dP^T u) (Simulation.cpp:1561-1600)
    * with a direct solve when the cap is hit (:1589-1594); 1 = always the direct solve, i.e. the semantics of
    * Simulation::backwardGradientForceDirectSolver / solveDirect (:1431-1440). On the GPU the direct solve is a
-   * block-Jacobi preconditioned BiCGSTAB on (P - dP^T) run to adjoint_rel_tol (relative residual; <=0: 1e-6). */
+   * block-Jacobi preconditioned BiCGSTAB on (P - dP^T) run to adjoint_rel_tol (relative residual; <=0: 1e-6).
+   * 2 = the dense direct solve, the counterpart of solveDirect's SparseLU: per rollout and step K = P - dP^T is assembled as a dense fp64
+   * matrix and factored by LU with partial pivoting on the device; u comes from forward / back substitution with the factors, refined
+   * against the fp64 residual (at most 3 substitutions) to adjoint_rel_tol; a rollout whose factorisation meets a zero or non-finite pivot
+   * takes the fp64 BiCGSTAB fall-back. Meshes of at most 768 vertices (dc_set_params / dc_build fail with DC_ERR_INVALID above);
+   * one backward step per launch, one workgroup per rollout. dc_set_solver(force_direct_adjoint = 1) keeps mode 2.            */
   int adjoint_mode;
   double adjoint_rel_tol;
   /* direct adjoint solve: 1 (default) = block-Jacobi preconditioner from the 3x3 diagonal blocks of K = P - dP^T itself, rebuilt
@@ -125,7 +130,9 @@ typedef struct dc_bwd_stats {
   int adjoint_iters;
   int cg_iters;
   int clipped;
-  int used_direct;       /* 1 when the direct (Krylov) solve ran; adjoint_iters then counts its iterations too */
+  int used_direct;       /* 1 when the direct (Krylov) solve ran; adjoint_iters then counts its iterations too; 2 = the dense direct solve
+                            (adjoint_mode 2): refine_cycles = substitutions with the LU factors, adjoint_iters = cg_iters = 0, fp64_iters =
+                            iterations of the fall-back, last_udiff = the fp64 residual |g - K u| / |g| (residual_verified = 1)            */
   float last_udiff;      /* mode 0: |u_new - u|_2 / N; direct solve: relative residual |g - K u| / |g| — mixed precision: the TRUE
                             residual evaluated in fp64 (residual_verified = 1), or, when the last fp32 correction solve was accepted
                             without a further fp64 evaluation, an upper bound: its recurrence residual + twice the measured fp32
@@ -360,6 +367,13 @@ int dc_timer_stop(dc_ctx *ctx, float *ms);
  * reset, measured with HIP events on the context's stream; used by bench.py's roofline block. A dc_rollout_* call
  * may run all its time steps in ONE launch (every rollout advances on its own), so launches <= steps.            */
 int dc_kernel_times(dc_ctx *ctx, float *fwd_ms, int *fwd_launches, float *bwd_ms, int *bwd_launches, int reset);
+/* Diagnostics of the dense direct adjoint solve (adjoint_mode 2, meshes of at most 768 vertices; any adjoint_mode may call it).
+ * dc_get_adjoint_matrix: K = P - dP^T of record `slot`, rollout `rollout`, as the device assembles it for the dense solve: (3N)^2 doubles,
+ * row-major, rows and columns xyz interleaved in the caller's vertex numbering (index 3 i + c) — the layout of the fp64 oracle's matrix.
+ * dc_dense_phase_times: accumulated device time (ms) of the mode-2 backward steps split into assembly, factorisation and solve; measured
+ * only when the environment sets DC_DENSE_TIMES=1 (each chunk then synchronises); reset != 0 zeroes them afterwards.            */
+int dc_get_adjoint_matrix(dc_ctx *ctx, int slot, int rollout, double *K /*(3N)^2*/);
+int dc_dense_phase_times(dc_ctx *ctx, float *ms3, int reset);
 
 #ifdef __cplusplus
 }
