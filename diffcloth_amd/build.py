@@ -1,6 +1,7 @@
 """Builds the native libraries of diffcloth_amd in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
-  libdiffcloth_hip.so   C-ABI engine (include/diffcloth_hip.h): host system builder + HIP kernels
+  libdiffcloth_hip.so       C-ABI engine (include/diffcloth_hip.h): host system builder + HIP kernels
+  libdc_dense_lu_check.so   test infrastructure (tests/native/dense_lu_check.hip): the dense adjoint solve's LU kernels on arbitrary matrices
 """
 import os
 import subprocess
@@ -23,14 +24,19 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def kernel_flags():
+    """the compile flags of every kernel translation unit: the engine's objects and the GPU check libraries"""
+    return [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function",
+            "-I", os.path.join(ROOT, "include")] + os.environ.get("DC_CXXFLAGS", "").split()   # e.g. -DDC_PROFILE_PHASES
+
+
 def build_engine(force=False, verbose=False):
     """Compiles every source to its own object (in parallel, only the stale ones) and links the shared library."""
     from concurrent.futures import ThreadPoolExecutor
     objdir = os.path.join(LIBDIR, "obj")
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")] + [os.path.join(ROOT, "include", "diffcloth_hip.h")]
-    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function",
-             "-I", os.path.join(ROOT, "include")] + os.environ.get("DC_CXXFLAGS", "").split()   # e.g. -DDC_PROFILE_PHASES
+    flags = kernel_flags()
     stamp = os.path.join(objdir, "flags.txt")
     if not os.path.exists(stamp) or open(stamp).read() != " ".join(flags):
         force = True
@@ -75,6 +81,38 @@ def build_pymodule(force=False, verbose=False):
     return out
 
 
+KERNEL_CHECKS = {"libdc_dense_lu_check.so": ("dense_lu_check.hip", ["dc_adjoint_dense.hip"])}
+
+
+def kernel_check_path(name="libdc_dense_lu_check.so"):
+    return os.path.join(LIBDIR, name)
+
+
+def build_kernel_checks(force=False, verbose=False):
+    """GPU check libraries of tests/native/*.hip: each includes a kernel translation unit of csrc as text (the same source, the engine's
+    flags) and exports a C function that runs its kernels on the caller's inputs. The GPU tests load them; they do not compile."""
+    os.makedirs(LIBDIR, exist_ok=True)
+    headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
+    flags = kernel_flags() + ["-I", CSRC]
+    outs = []
+    for lib, (src, tus) in KERNEL_CHECKS.items():
+        src = os.path.join(ROOT, "tests", "native", src)
+        out = kernel_check_path(lib)
+        outs.append(out)
+        stamp = out + ".flags.txt"
+        same_flags = os.path.exists(stamp) and open(stamp).read() == " ".join(flags)
+        if not force and same_flags and not _stale(out, [src] + [os.path.join(CSRC, t) for t in tus] + headers):
+            continue
+        cmd = [HIPCC] + flags + ["-shared", "-o", out, src]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+        with open(stamp, "w") as f:
+            f.write(" ".join(flags))
+    return outs
+
+
 if __name__ == "__main__":
     print(build_engine(force="--force" in sys.argv, verbose=True))
+    print(build_kernel_checks(force="--force" in sys.argv, verbose=True))
     print(build_pymodule(force="--force" in sys.argv, verbose=True))

@@ -485,7 +485,9 @@ int check_dense_mode(dc_ctx *c, int mode, int N, const char *who) {
 }
 
 // Scratch of the dense adjoint solve, on first use: as many rollouts per chunk as fit a budget of 8 GB (DC_DENSE_CHUNK=k caps the chunk at
-// k rollouts, development switch: the chunked path on small batches)
+// k rollouts, development switch: the chunked path on small batches). DC_DENSE_FLAG=b, development switch read by enqueue_dense_adjoint:
+// rollout b is marked as if its factorisation had met a zero pivot (no valid scene does), so its adjoint step takes the fp64 BiCGSTAB
+// fall-back from u = 0; the other rollouts are untouched.
 int dense_ensure(dc_ctx *c) {
   if (c->dense.K) return DC_OK;
   const int N = c->host.N, ld = dense_adj_ld(N), cap = std::max(c->self_cap, 1);
@@ -518,10 +520,14 @@ int enqueue_dense_adjoint(dc_ctx *c, const BwdArgs &A) {
   if ((rc = dense_ensure(c))) return rc;
   const DenseAdjWork &D = c->dense;
   const int n = 3 * c->host.N;
+  static const int one = 1;
+  const char *envf = getenv("DC_DENSE_FLAG");
+  const int forced = (envf && envf[0] >= '0' && envf[0] <= '9') ? atoi(envf) : -1;
   for (int b0 = 0; b0 < c->B; b0 += c->dense_nb) {
     const int nb = std::min(c->dense_nb, c->B - b0);
     if (c->dense_timing) HIPCHK(c, hipEventRecord(c->ev_d[0], c->stream));
     HIPCHK(c, hipMemsetAsync(D.flag, 0, sizeof(int) * nb, c->stream));
+    if (forced >= b0 && forced < b0 + nb) HIPCHK(c, hipMemcpyAsync(D.flag + (forced - b0), &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
     launch_dense_assemble(c->S, A, c->W.x64, D, b0, nb, c->stream);
     if (c->dense_timing) HIPCHK(c, hipEventRecord(c->ev_d[1], c->stream));
     c->dense_launches += 2 + launch_dense_factor(D, n, nb, c->stream);
