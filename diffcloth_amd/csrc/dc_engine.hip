@@ -1,33 +1,16 @@
 // C-ABI layer of libdiffcloth_hip.so: context, device memory, tape, and the calls that enqueue the
 // persistent step kernels. See include/diffcloth_hip.h for the contract of every entry point.
 #include <hip/hip_runtime.h>
-// RCCL is bound with dlopen in dc_comm_* (no link-time and no header dependency): the handful of types and constants of its C API
-// (rccl.h / nccl.h) the four entry points used here need, restated
-extern "C" {
-typedef struct ncclComm *ncclComm_t;
-typedef struct { char internal[128]; } ncclUniqueId;
-typedef enum { ncclSuccess = 0 } ncclResult_t;
-typedef enum { ncclFloat64 = 8 } ncclDataType_t;      // ncclDouble
-typedef enum { ncclSum = 0 } ncclRedOp_t;
-#define NCCL_UNIQUE_ID_BYTES 128
-}
-#include <dlfcn.h>
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
-#include "dc_device.h"
-#include "dc_system.h"
-#include "dc_windows.h"
-#include "dc_packets.h"
-#include "dc_dense.h"
-#include "dc_deflate.h"
+#include "dc_context.h"
+#include "dc_tables.h"
 #include "dc_spheremesh.h"
 #include "dc_selftmp.h"
-#include "dc_cluster.h"
-#include "dc_adjoint_dense.h"
 
 using namespace dc;
 
@@ -36,109 +19,7 @@ hipError_t launch_pd_step_cluster(const DevSystem &S, const DevCluster &CL, cons
 hipError_t launch_adjoint_step_cluster(const DevSystem &S, const DevCluster &CL, const DevWork &W, const BwdArgs &A, int b0, int nb, hipStream_t st);
 }
 
-// Tables of the split kernels (dc_cluster.h) for one K, built when the batch size is known (dc_alloc_batch).
-struct ClusterSet {
-  bool ok = false;
-  int K = 1, nb = 0;              // workgroups per rollout; rollouts per launch (K nb <= CUs)
-  DevCluster D;
-  std::vector<void *> allocs;
-  size_t xch_bytes = 0;
-};
-
-struct dc_ctx {
-  int device = 0;
-  bool host_only = false;   // dc_create(-1): table building / inspection only, every compute call fails
-  hipStream_t stream = nullptr;
-  hipStream_t own_stream = nullptr; // the stream dc_create made (dc_use_stream may point `stream` at the caller's)
-  std::string err;
-  HostSystem host;
-  dc_params params;
-  std::vector<dc_primitive> prims;
-  std::vector<int> group_of_prim;
-  int ngroups = 0;
-  bool mesh_set = false, built = false;
-  // vertex renumbering on the device (empty = identity): user_of[device index] = caller's index, dev_of = inverse
-  std::vector<int> user_of, dev_of;
-  std::vector<int> att_user;        // attachment vertices in the caller's numbering
-  const int *d_user_of = nullptr;   // device copy of user_of (null = identity)
-
-  DevSystem S;
-  std::vector<void *> table_allocs;
-
-  int B = 0, tape = 0;
-  DevWork W;
-  std::vector<void *> batch_allocs;
-  float *X = nullptr, *V = nullptr, *F = nullptr, *R = nullptr, *NRM = nullptr;   // [(tape+1)][B][3][N]
-  int *PRIM = nullptr;                                                            // [(tape+1)][B][N]
-  int2 *SC_pair = nullptr;          // [(tape+1)][B][cap] self contacts per record
-  float4 *SC_nrm = nullptr, *SC_d = nullptr;
-  int *SC_meta = nullptr;           // [(tape+1)][B][kMetaStride]
-  int *SC_verts = nullptr;          // [(tape+1)][B][2 * cap] working-set vertex lists of the self contacts
-  int self_cap = 0;
-  float *xf_cur = nullptr;          // [B][3][Af]
-  float *XF = nullptr;              // [(tape+1)][B][3][Af] fixed-point targets per record
-  float *DPAR = nullptr;            // [(tape+1)][B][8] per-step parameter gradients
-  float *mu = nullptr, *fu = nullptr;
-  bool fu_set = false;
-  float *fv = nullptr;              // [B][3][N] per-vertex extra force
-  bool fv_set = false;
-  float *fv2 = nullptr;             // [B][3][N] second per-vertex force term, factor 1 (dc_set_vertex_force_field)
-  bool fv2_set = false;
-  int start_slot = 0;              // dc_set_trajectory_start: the tape slot of the trajectory's initial state (-1: none in this tape)
-  float *GX = nullptr, *GV = nullptr, *IX = nullptr, *IV = nullptr, *DMU = nullptr, *target = nullptr;
-  float *DXF = nullptr;             // [(tape+1)][B][3][Af] dL_dxfixed of the step that produced the slot
-  // device-resident schedules of the fused rollouts (dc_set_*_schedule); flags per tape slot
-  float *FU_S = nullptr;            // [(tape+1)][B][3] uniform force of the step that produces the slot
-  float *FVS_S = nullptr;           // [(tape+1)][B] factor on fv of that step
-  float *SEEDX = nullptr, *SEEDV = nullptr;   // [(tape+1)][B][3][N] loss gradient w.r.t. the state at the slot (allocated on first use)
-  std::vector<char> sched_xf, sched_fu, sched_fvs, sched_seed;
-  void *comm = nullptr;             // RCCL communicator of dc_comm_init (ncclComm_t), one rank per context
-  int comm_ranks = 0;
-  std::vector<void *> sched_pool;
-  // record handed in from outside (dc_set_record): fp64 values of x_new, f, primitive-contact normals [B][3][N], self-contact normals / d
-  // [B][cap][3]; allocated on first use, valid for tape slot inj_slot only (-1 = none)
-  float *YS = nullptr;              // [(tape+1)][B][3][N] y of every backward step (dc_keep_force_gradients), allocated on first use
-  bool keep_y = false;
-  double *INJ_X = nullptr, *INJ_F = nullptr, *INJ_N = nullptr, *INJ_SN = nullptr, *INJ_SD = nullptr;
-  int inj_slot = -1;
-  dc_step_stats *fstats = nullptr;  // [(tape+1)][B]
-  dc_bwd_stats *bstats = nullptr;   // [(tape+1)][B], indexed by the slot whose record was differentiated
-  double *stage[4] = {nullptr, nullptr, nullptr, nullptr};
-  size_t stage_elems = 0;
-  hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
-  float fwd_ms = 0, bwd_ms = 0;
-  int fwd_launches = 0, bwd_launches = 0;
-  ClusterSet cl;
-  int cus = 0;                      // compute units of the device
-  int bandwidth = 0;                // of the scalar system matrix in device numbering
-  int defl_k = 0, defl_probe = 0;   // deflation space of the forward solve (dc_deflate.h)
-  // the last deflation build of this context and what it was built from: a rebuild that leaves P unchanged (another tolerance, contact flags,
-  // primitives ...) skips the probe solve and the eigen-solve (0.9 s on the 7 742-vertex dress)
-  HostDeflation defl_cache;
-  uint64_t defl_key = 0;
-  bool defl_cache_valid = false, defl_cache_built = false;
-  // dense direct adjoint solve (adjoint_mode 2, dc_adjoint_dense.h): matrices / factors of a chunk of dense_nb rollouts, allocated in the
-  // batch pool on the first mode-2 backward step; phase times (assembly, factorisation, solve) when DC_DENSE_TIMES=1
-  DenseAdjWork dense{};
-  int dense_nb = 0;
-  int dense_launches = 0;           // kernel launches of the mode-2 backward steps enqueued (counter; dc_rollout_backward adds the difference)
-  bool dense_timing = false;
-  float dense_ms[3] = {0, 0, 0};
-  hipEvent_t ev_d[4] = {nullptr, nullptr, nullptr, nullptr};
-};
-
 namespace {
-
-int fail(dc_ctx *c, int code, const std::string &msg) {
-  if (c) c->err = msg;
-  return code;
-}
-#define HIPCHK(c, call)                                                                         \
-  do {                                                                                          \
-    hipError_t e_ = (call);                                                                     \
-    if (e_ != hipSuccess)                                                                       \
-      return fail(c, DC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));            \
-  } while (0)
 
 template <typename T>
 int dev_alloc(dc_ctx *c, std::vector<void *> &pool, T **out, size_t count) {
@@ -160,11 +41,32 @@ int upload(dc_ctx *c, const T **out, const std::vector<U> &src) {
   *out = p;
   return DC_OK;
 }
+// the same, behind a pointer to the kernels' vector type (int2 / int4 / float2 / float4 tables are built as flat arrays of T)
+template <typename T, typename V, typename U>
+int upload_as(dc_ctx *c, const V **out, const std::vector<U> &src) {
+  const T *p = nullptr;
+  const int rc = upload<T>(c, &p, src);
+  *out = (const V *) p;
+  return rc;
+}
 void free_pool(std::vector<void *> &pool) {
   for (void *p : pool) (void) hipFree(p);
   pool.clear();
 }
+// elements of one tape slot of the per-vertex arrays / of the fixed-point arrays, and the slots of the per-record arrays
 size_t slot_elems(const dc_ctx *c) { return (size_t) c->B * 3 * c->host.N; }
+size_t xf_elems(const dc_ctx *c) { return (size_t) c->B * 3 * c->S.Af; }
+float *xf_slot(const dc_ctx *c, int slot) { return c->XF + xf_elems(c) * slot; }
+float *dxf_slot(const dc_ctx *c, int slot) { return c->DXF + xf_elems(c) * slot; }
+float *dpar_slot(const dc_ctx *c, int slot) { return c->DPAR + (size_t) c->B * 8 * slot; }
+float *seedx_slot(const dc_ctx *c, int slot) { return c->SEEDX + slot_elems(c) * slot; }
+float *seedv_slot(const dc_ctx *c, int slot) { return c->SEEDV + slot_elems(c) * slot; }
+SelfRec self_slot(const dc_ctx *c, int slot) {      // self contacts of record `slot`
+  const size_t sc = (size_t) c->B * c->self_cap * slot, sm = (size_t) c->B * kMetaStride * slot;
+  SelfRec R;
+  R.pair = c->SC_pair + sc; R.nrm = c->SC_nrm + sc; R.dvec = c->SC_d + sc; R.meta = c->SC_meta + sm; R.verts = c->SC_verts + 2 * sc;
+  return R;
+}
 
 int pd_cap(const dc_ctx *c) {
   if (c->params.pd_iter_cap >= 0) return c->params.pd_iter_cap;
@@ -214,15 +116,11 @@ FwdArgs fwd_args(dc_ctx *c, int slot) {
   A.fv2 = c->fv2_set ? c->fv2 : nullptr;
   A.fv_scale = nullptr; A.slot_xfix = 0; A.slot_fu = 0; A.slot_fvs = 0;
   // scheduled values of this step (dc_set_*_schedule) take precedence over the current ones
-  if (c->S.Af > 0 && c->sched_xf[slot + 1]) A.x_fixed = c->XF + (size_t) c->B * 3 * c->S.Af * (slot + 1);
+  if (c->S.Af > 0 && c->sched_xf[slot + 1]) A.x_fixed = xf_slot(c, slot + 1);
   if (c->sched_fu[slot + 1]) A.fu = c->FU_S + (size_t) c->B * 3 * (slot + 1);
   if (c->sched_fvs[slot + 1] && A.fv) A.fv_scale = c->FVS_S + (size_t) c->B * (slot + 1);
   A.stats = c->fstats + (size_t) c->B * (slot + 1);
-  {
-    const size_t sc = (size_t) c->B * c->self_cap * (slot + 1), sm = (size_t) c->B * kMetaStride * (slot + 1);
-    A.self.pair = c->SC_pair + sc; A.self.nrm = c->SC_nrm + sc; A.self.dvec = c->SC_d + sc; A.self.meta = c->SC_meta + sm;
-    A.self.verts = c->SC_verts + 2 * sc;
-  }
+  A.self = self_slot(c, slot + 1);
   A.fwd_tol = (float) c->params.forward_tol;
   A.cg_tol = (float) (c->params.cg_rel_tol > 0 ? c->params.cg_rel_tol : 1e-4);
   A.pd_cap = pd_cap(c);
@@ -240,19 +138,15 @@ BwdArgs bwd_args(dc_ctx *c, int slot, bool is_start, bool with_init) {
   BwdArgs A;
   A.x_new = c->X + se * slot; A.rec_f = c->F + se * slot; A.rec_n = c->NRM + se * slot;
   A.rec_prim = c->PRIM + sp * slot; A.mu = c->mu;
-  {
-    const size_t sc = (size_t) c->B * c->self_cap * slot, sm = (size_t) c->B * kMetaStride * slot;
-    A.self.pair = c->SC_pair + sc; A.self.nrm = c->SC_nrm + sc; A.self.dvec = c->SC_d + sc; A.self.meta = c->SC_meta + sm;
-    A.self.verts = c->SC_verts + 2 * sc;
-  }
+  A.self = self_slot(c, slot);
   A.gx = c->GX; A.gv = c->GV;
   A.ix = with_init ? c->IX : nullptr; A.iv = with_init ? c->IV : nullptr; A.slot_ix = 0;
   if (!with_init && c->SEEDX && c->sched_seed[slot - 1]) {      // seed schedule: the loss gradient w.r.t. the state this step started from
-    A.ix = c->SEEDX + se * (slot - 1); A.iv = c->SEEDV + se * (slot - 1); A.slot_ix = se;
+    A.ix = seedx_slot(c, slot - 1); A.iv = seedv_slot(c, slot - 1); A.slot_ix = se;
   }
-  A.d_xfixed = c->DXF + (size_t) c->B * 3 * c->S.Af * slot; A.d_mu = c->DMU;
-  A.d_param = c->DPAR + (size_t) c->B * 8 * slot;
-  A.x_fixed = c->XF + (size_t) c->B * 3 * c->S.Af * slot;
+  A.d_xfixed = dxf_slot(c, slot); A.d_mu = c->DMU;
+  A.d_param = dpar_slot(c, slot);
+  A.x_fixed = xf_slot(c, slot);
   A.x_prev = c->X + se * (slot - 1); A.v_prev = c->V + se * (slot - 1); A.v_new = c->V + se * slot; A.stats = c->bstats + (size_t) c->B * slot;
   A.bwd_tol = (float) c->params.backward_tol;
   A.cg_tol = (float) (c->params.cg_rel_tol > 0 ? c->params.cg_rel_tol : 1e-4);
@@ -277,14 +171,12 @@ BwdArgs bwd_args(dc_ctx *c, int slot, bool is_start, bool with_init) {
   A.inj_sn = inj ? c->INJ_SN : nullptr; A.inj_sd = inj ? c->INJ_SD : nullptr;
   A.ys = (c->keep_y && c->YS) ? c->YS + se * slot : nullptr;
   A.slot_state = se; A.slot_prim = sp; A.slot_self = (size_t) c->B * c->self_cap; A.slot_meta = (size_t) c->B * kMetaStride;
-  A.slot_param = (size_t) c->B * 8; A.slot_xf = (size_t) c->B * 3 * c->S.Af; A.slot_stats = (size_t) c->B;
+  A.slot_param = (size_t) c->B * 8; A.slot_xf = xf_elems(c); A.slot_stats = (size_t) c->B;
   return A;
 }
 
 
 // ---- split execution (dc_cluster.h): choice of K, tables, launches ------------------------------------------------------------
-static int round64(int v) { return (v + 63) / 64 * 64; }
-
 void free_cluster(dc_ctx *c) {
   for (void *p : c->cl.allocs) (void) hipFree(p);
   c->cl = ClusterSet();
@@ -422,6 +314,13 @@ static bool build_deflation_cached(dc_ctx *c, const HostSystem &H, int want, int
   return c->defl_cache_built;
 }
 
+// DevSystem fields both kinds of context take from the table plan: the kernel set dc_get_layout reports, and what sizes the batch
+static void set_decisions(DevSystem &S, const HostTables &plan) {
+  S.win_ok = plan.win_ok; S.nwin = plan.nwin; S.pk_ok = plan.pk_ok; S.pk_vpt = plan.pk_vpt; S.pk_threads = plan.pk_threads;
+  S.fwd_defl = plan.fwd_defl; S.adj_coarse = plan.adj_coarse; S.dense_ld = plan.dense_ld;
+  S.max_radii = plan.max_radii; S.self_cap = plan.self_cap; S.self_lds = plan.self_lds;
+}
+
 // K for this batch: enough parts to give every CU a workgroup (B rollouts x K <= CUs, K <= 8), at least as many as a mesh too
 // large for the one-workgroup kernel needs; DC_CLUSTER=k forces k (development switch; 0 / 1 = off).
 int choose_cluster(dc_ctx *c) {
@@ -461,7 +360,6 @@ int choose_cluster(dc_ctx *c) {
 // The error word of the split kernels is sticky on the device: it is zero until an exchange times out and is cleared only AFTER that
 // has been reported — an asynchronous call (dc_step_forward without statistics, dc_step_backward ...) can therefore not lose a
 // time-out to the next call: whichever synchronising call comes first (statistics, dc_get_state / gradient / record, dc_sync) reports it.
-int cluster_begin(dc_ctx *) { return DC_OK; }
 int cluster_check(dc_ctx *c) {       // after a synchronisation
   if (!c->cl.ok) return DC_OK;
   unsigned e[4] = {0, 0, 0, 0};
@@ -568,6 +466,68 @@ int enqueue_adjoint_step(dc_ctx *c, const BwdArgs &A) {
     HIPCHK(c, launch_adjoint_step_cluster(c->S, c->cl.D, c->W, A, b0, std::min(c->cl.nb, c->B - b0), c->stream));
   }
   return DC_OK;
+}
+
+// DC_FUSE_STEPS=0 (development switch, read once per process): one launch per step in dc_rollout_forward / dc_rollout_backward
+bool fuse_steps_enabled() {
+  static const bool on = !(getenv("DC_FUSE_STEPS") && getenv("DC_FUSE_STEPS")[0] == '0');
+  return on;
+}
+
+// The forward steps slot -> slot + 1 ... -> slot + nsteps, enqueued on the context's stream: the targets of every step that has no schedule entry
+// (dc_set_fixed_point_schedule) go from xf_cur into the step's XF slot, then self-collision detection and the step kernel per step, or, fused,
+// all steps of a rollout inside ONE launch (detection inlined per step), so that a rollout never waits for the slowest rollout of the batch
+// between steps. carry_targets (the rollout call; the per-step calls leave xf_cur alone): later unscheduled steps continue from the last
+// scheduled targets. Returns the number of step-kernel launches per chunk of rollouts in *launches.
+int enqueue_forward_steps(dc_ctx *c, int slot, int nsteps, bool carry_targets, int *launches) {
+  const bool self_on = c->S.contact_enabled && c->S.self_enabled, has_xf = c->S.Af > 0;
+  const bool fused = fuse_steps_enabled() && nsteps > 1 && (use_cluster_fwd(c) || pd_step_fusable(c->S));
+  const size_t xf_bytes = sizeof(float) * xf_elems(c);
+  int rc;
+  FwdArgs FA = fwd_args(c, slot);          // fused: points x_fixed / fu / fv_scale at the first step's schedule entries
+  if (fused) {      // a schedule (dc_set_*_schedule) has to cover all steps of a fused sweep or none of them
+    int nxf = 0, nfu = 0, nfvs = 0;
+    for (int k = 1; k <= nsteps; k++) { nxf += c->sched_xf[slot + k]; nfu += c->sched_fu[slot + k]; nfvs += c->sched_fvs[slot + k]; }
+    if ((nxf % nsteps) || (nfu % nsteps) || (nfvs % nsteps))
+      return fail(c, DC_ERR_INVALID, "dc_rollout_forward: a fixed-point / force schedule covers only part of the steps " + std::to_string(slot) + " .. " + std::to_string(slot + nsteps));
+    if (nxf) FA.slot_xfix = xf_elems(c);
+    if (nfu) FA.slot_fu = (size_t) c->B * 3;
+    if (nfvs && FA.fv_scale) FA.slot_fvs = (size_t) c->B;
+    FA.nsteps = nsteps; FA.inline_detect = self_on ? 1 : 0;
+  }
+  for (int k = 0; k < nsteps; k++) {
+    if (has_xf && !c->sched_xf[slot + k + 1]) HIPCHK(c, hipMemcpyAsync(xf_slot(c, slot + k + 1), c->xf_cur, xf_bytes, hipMemcpyDeviceToDevice, c->stream));
+    if (fused) continue;
+    if (k) FA = fwd_args(c, slot + k);
+    if (self_on) launch_self_detect(c->S, c->W, FA, c->B, c->stream);
+    if ((rc = enqueue_pd_step(c, FA))) return rc;
+  }
+  if (fused && (rc = enqueue_pd_step(c, FA))) return rc;
+  if (carry_targets && has_xf && c->sched_xf[slot + nsteps])
+    HIPCHK(c, hipMemcpyAsync(c->xf_cur, xf_slot(c, slot + nsteps), xf_bytes, hipMemcpyDeviceToDevice, c->stream));
+  if (launches) *launches = fused ? 1 : nsteps;
+  return DC_OK;
+}
+
+// The bracket of dc_kernel_times around the enqueues of a rollout call: begin before the first, end after the last. end waits for the sweep,
+// adds its time and its launches (`launches` per chunk of rollouts of the split kernels; adjoint_mode 2: what enqueue_dense_adjoint counted)
+// and reports a time-out of the split kernels.
+int kernel_time_begin(dc_ctx *c) {
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventRecord(c->ev_a, c->stream));
+  c->dense_mark = c->dense_launches;
+  return DC_OK;
+}
+int kernel_time_end(dc_ctx *c, bool bwd, int launches) {
+  HIPCHK(c, hipEventRecord(c->ev_b, c->stream));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventSynchronize(c->ev_b));
+  float ms = 0;
+  HIPCHK(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
+  const int chunks = (bwd ? use_cluster_bwd(c) : use_cluster_fwd(c)) ? (c->B + c->cl.nb - 1) / c->cl.nb : 1;
+  (bwd ? c->bwd_ms : c->fwd_ms) += ms;
+  (bwd ? c->bwd_launches : c->fwd_launches) += (bwd && c->params.adjoint_mode == 2) ? c->dense_launches - c->dense_mark : launches * chunks;
+  return cluster_check(c);
 }
 
 }  // namespace
@@ -720,19 +680,25 @@ int dc_build(dc_ctx *c) {
     if (!c->dev_of.empty()) a = c->dev_of[a];
   }
   if (!H.build_numerics(p.time_step, p.density, p.k_stretch, p.k_bend, p.k_att)) return fail(c, DC_ERR_TOPOLOGY, H.error);
-  c->bandwidth = 0;
-  for (int r = 0; r < H.N; r++)
-    for (int k = H.P_ptr[r]; k < H.P_ptr[r + 1]; k++) c->bandwidth = std::max(c->bandwidth, std::abs(H.P_col[k] - r));
-  if (c->host_only) {       // which kernel set this system would get (dc_get_layout): the same host-side table builders, nothing uploaded
-    HostWindows HW; HostPackets HP;
-    c->S.win_ok = HW.build(H, (size_t) 150 * 1024) ? 1 : 0;
-    c->S.pk_ok = HP.build(H) ? 1 : 0;
-    c->S.nwin = HW.nwin; c->S.pk_vpt = HP.vpt; c->S.pk_threads = HP.threads;
-    {
-      HostDeflation *HD = nullptr;
-      c->defl_k = 0; c->defl_probe = 0;
-      if (c->S.win_ok) { build_deflation_cached(c, H, deflation_want(p), c->S.pk_ok ? HP.threads * HP.vpt : round64(H.N), &HD); c->defl_k = HD->k; c->defl_probe = HD->probe_iterations; }
-    }
+  // every table and every kernel-set decision comes from the host-side plan (dc_tables.h); the development switches that gate tables are read here
+  TableSwitches sw;
+  { const char *envw = getenv("DC_WINDOWS"); sw.windows = !(envw && envw[0] == '0'); }        // 0 keeps the global-memory corner passes
+  { const char *envd = getenv("DC_DENSE_MAX_N"); sw.dense_max_n = envd ? atoi(envd) : kDenseMaxN; }   // 0 disables, other values move the size limit
+                                                    // (default 2.4 MB: the matrix must stay in every XCD's 4 MB L2 next to the other tables)
+  { const char *envs = getenv("DC_SELF_LDS"); sw.self_lds = !(envs && envs[0] == '0'); }      // 0 = global-memory layer passes
+  static const char *envc = getenv("DC_ADJ_COARSE");      // 0 = block preconditioner only in the adjoint's fall-back
+  sw.adj_coarse = !(envc && atoi(envc) == 0);
+  HostTables plan;
+  plan.build(H, p, sw);
+  HostDeflation *HD = nullptr;
+  const bool defl = plan.defl_rows > 0 && build_deflation_cached(c, H, deflation_want(p), plan.defl_rows, &HD);
+  plan.set_deflation(defl, sw);
+  c->bandwidth = plan.bandwidth;
+  c->defl_k = HD ? HD->k : 0; c->defl_probe = HD ? HD->probe_iterations : 0;
+  DevSystem &S = c->S;
+  if (c->host_only) {       // which kernel set this system would get (dc_get_layout): the same plan, nothing uploaded
+    std::memset(&S, 0, sizeof(S));
+    set_decisions(S, plan);
     c->built = true;
     return DC_OK;
   }
@@ -740,68 +706,34 @@ int dc_build(dc_ctx *c) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   free_cluster(c);
   free_pool(c->table_allocs);
-  DevSystem &S = c->S;
   std::memset(&S, 0, sizeof(S));
-  const int N = H.N, T = H.T, E = H.E, Af = (int) H.att_vertex.size();
-  S.N = N; S.T = T; S.E = E; S.Af = Af; S.NC = 3 * T + 4 * E;
-  S.user_of = nullptr; S.dev_of = nullptr; c->d_user_of = nullptr;
+  set_decisions(S, plan);
+  S.N = H.N; S.T = H.T; S.E = H.E; S.Af = (int) H.att_vertex.size(); S.NC = 3 * H.T + 4 * H.E;
+  c->d_user_of = nullptr;
+  int rc;
   if (!c->user_of.empty()) {
-    int rcp;
-    if ((rcp = upload<int>(c, &S.user_of, c->user_of))) return rcp;
-    if ((rcp = upload<int>(c, &S.dev_of, c->dev_of))) return rcp;
+    if ((rc = upload<int>(c, &S.user_of, c->user_of))) return rc;
+    if ((rc = upload<int>(c, &S.dev_of, c->dev_of))) return rc;
     c->d_user_of = S.user_of;
   }
-  // planar index tables
-  std::vector<int> triv(3 * (size_t) T), bendv(4 * (size_t) E);
-  for (int t = 0; t < T; t++) for (int k = 0; k < 3; k++) triv[(size_t) k * T + t] = H.tri[3 * t + k];
-  for (int e = 0; e < E; e++) for (int k = 0; k < 4; k++) bendv[(size_t) k * E + e] = H.bend_v[4 * e + k];
-  std::vector<float> bendnw(2 * (size_t) E), dinv(N);
-  for (int e = 0; e < E; e++) { bendnw[2 * e] = (float) H.bend_n[e]; bendnw[2 * e + 1] = (float) H.bend_w2[e]; }
-  for (int i = 0; i < N; i++) {
-    double d = 0;
-    for (int k = H.P_ptr[i]; k < H.P_ptr[i + 1]; k++) if (H.P_col[k] == i) d = H.P_val[k];
-    dinv[i] = (float) (1.0 / d);
-  }
-  std::vector<int> att_of(N, -1);
-  for (int a = 0; a < Af; a++) att_of[H.att_vertex[a]] = a;
-  int rc;
-  const float *f4;
-  if ((rc = upload<int>(c, &S.tri_v, triv))) return rc;
-  if ((rc = upload<float>(c, &f4, H.tri_D))) return rc;
-  S.tri_D = (const float4 *) f4;
+  if ((rc = upload<int>(c, &S.tri_v, plan.tri_v))) return rc;
+  if ((rc = upload_as<float>(c, &S.tri_D, H.tri_D))) return rc;
   if ((rc = upload<float>(c, &S.tri_w2, H.tri_w2))) return rc;
-  if ((rc = upload<int>(c, &S.bend_v, bendv))) return rc;
-  if ((rc = upload<float>(c, &f4, H.bend_w))) return rc;
-  S.bend_w = (const float4 *) f4;
-  if ((rc = upload<float>(c, &f4, bendnw))) return rc;
-  S.bend_nw = (const float2 *) f4;
+  if ((rc = upload<int>(c, &S.bend_v, plan.bend_v))) return rc;
+  if ((rc = upload_as<float>(c, &S.bend_w, H.bend_w))) return rc;
+  if ((rc = upload_as<float>(c, &S.bend_nw, plan.bend_nw))) return rc;
   if ((rc = upload<int>(c, &S.att_vertex, H.att_vertex))) return rc;
-  if ((rc = upload<int>(c, &S.att_of_vertex, att_of))) return rc;
+  if ((rc = upload<int>(c, &S.att_of_vertex, plan.att_of_vertex))) return rc;
   if ((rc = upload<float>(c, &S.mass, H.mass))) return rc;
-  if ((rc = upload<float>(c, &S.dinv, dinv))) return rc;
-  {  // fp64 rest-shape tables of the adjoint's fp64 operator (dc_adjoint64.h), planar
-    std::vector<double> d4(4 * (size_t) T), w4(4 * (size_t) E), nw2(2 * (size_t) E);
-    for (int t = 0; t < T; t++) for (int k = 0; k < 4; k++) d4[(size_t) k * T + t] = H.tri_D[4 * (size_t) t + k];
-    for (int e = 0; e < E; e++) {
-      for (int k = 0; k < 4; k++) w4[(size_t) k * E + e] = H.bend_w[4 * (size_t) e + k];
-      nw2[e] = H.bend_n[e]; nw2[(size_t) E + e] = H.bend_w2[e];
-    }
-    if ((rc = upload<double>(c, &S.tri_D64, d4))) return rc;
-    if ((rc = upload<double>(c, &S.tri_w2_64, H.tri_w2))) return rc;
-    if ((rc = upload<double>(c, &S.bend_w64, w4))) return rc;
-    if ((rc = upload<double>(c, &S.bend_nw64, nw2))) return rc;
-    if ((rc = upload<double>(c, &S.mass64, H.mass))) return rc;
-    std::vector<float> dlo(4 * (size_t) T), blo(4 * (size_t) E);
-    for (size_t k = 0; k < dlo.size(); k++) dlo[k] = (float) (H.tri_D[k] - (double) (float) H.tri_D[k]);
-    for (int e = 0; e < E; e++) {
-      for (int k = 1; k < 4; k++) blo[4 * (size_t) e + k - 1] = (float) (H.bend_w[4 * (size_t) e + k] - (double) (float) H.bend_w[4 * (size_t) e + k]);
-      blo[4 * (size_t) e + 3] = (float) (H.bend_n[e] - (double) (float) H.bend_n[e]);
-    }
-    if ((rc = upload<float>(c, &f4, dlo))) return rc;
-    S.tri_Dlo = (const float4 *) f4;
-    if ((rc = upload<float>(c, &f4, blo))) return rc;
-    S.bend_lo = (const float4 *) f4;
-  }
+  if ((rc = upload<float>(c, &S.dinv, plan.dinv))) return rc;
+  // fp64 rest-shape tables of the adjoint's fp64 operator (dc_adjoint64.h), planar, and their fp32 low parts
+  if ((rc = upload<double>(c, &S.tri_D64, plan.tri_D64))) return rc;
+  if ((rc = upload<double>(c, &S.tri_w2_64, H.tri_w2))) return rc;
+  if ((rc = upload<double>(c, &S.bend_w64, plan.bend_w64))) return rc;
+  if ((rc = upload<double>(c, &S.bend_nw64, plan.bend_nw64))) return rc;
+  if ((rc = upload<double>(c, &S.mass64, H.mass))) return rc;
+  if ((rc = upload_as<float>(c, &S.tri_Dlo, plan.tri_Dlo))) return rc;
+  if ((rc = upload_as<float>(c, &S.bend_lo, plan.bend_lo))) return rc;
   if ((rc = upload<int>(c, &S.P_ptr, H.P_ptr))) return rc;
   if ((rc = upload<int>(c, &S.P_col, H.P_col))) return rc;
   if ((rc = upload<float>(c, &S.P_val, H.P_val))) return rc;
@@ -810,121 +742,35 @@ int dc_build(dc_ctx *c) {
   if ((rc = upload<float>(c, &S.radii, H.radii))) return rc;
   if ((rc = upload<int>(c, &S.conn_ptr, H.conn_ptr))) return rc;
   if ((rc = upload<int>(c, &S.conn_idx, H.conn_idx))) return rc;
-  {
-    double mr = H.radii.empty() ? 0.0 : H.radii[0];
-    for (double r : H.radii) mr = std::max(mr, r);
-    S.max_radii = (float) mr;
-    // capacity of the per-rollout contact list: the caller's, or sized from the mesh (a fold brings every vertex of the upper
-    // layer into contact with one of the lower: ~N/2 pairs). Slots of the working set are 16-bit: at most 16000 pairs.
-    S.self_cap = std::min(p.max_self_contacts > 0 ? p.max_self_contacts : std::max(2048, N), 16000);
-    { const char *envs = getenv("DC_SELF_LDS"); S.self_lds = !(envs && envs[0] == '0'); }   // development switch: 0 = global-memory layer passes
+  if ((rc = upload_as<int>(c, &S.ell, plan.ell))) return rc;
+  if ((rc = upload<int>(c, &S.ell_ptr, plan.ell_ptr))) return rc;
+  if ((rc = upload<int>(c, &S.ell_w, plan.ell_w))) return rc;
+  if (plan.win_ok) {
+    const HostWindows &HW = plan.win;
+    if ((rc = upload_as<int>(c, &S.win, HW.win))) return rc;
+    if ((rc = upload_as<int>(c, &S.wtri_rec, HW.tri_rec))) return rc;
+    if ((rc = upload_as<float>(c, &S.wtri_D, HW.tri_D))) return rc;
+    if ((rc = upload_as<int>(c, &S.wbend_rec, HW.bend_rec))) return rc;
+    if ((rc = upload_as<float>(c, &S.wbend_w, HW.bend_w))) return rc;
+    if ((rc = upload_as<float>(c, &S.wtri_Dlo, HW.tri_Dlo))) return rc;
+    if ((rc = upload_as<float>(c, &S.wbend_lo, HW.bend_lo))) return rc;
+    if ((rc = upload_as<int>(c, &S.winc, HW.inc))) return rc;
+    if ((rc = upload<int>(c, &S.winc_ptr, HW.inc_ptr))) return rc;
+    if ((rc = upload<int>(c, &S.winc_n, HW.inc_n))) return rc;
+    S.win_vcap = HW.vcap; S.win_nrcap = HW.nrcap; S.win_lds_bytes = (int) HW.lds_bytes;
   }
-  {  // wave-sliced ELL copy of P for the LDS-resident PCG
-    const int nchunks = (N + 63) / 64;
-    std::vector<int> eptr(nchunks), ew(nchunks);
-    std::vector<int> flat;   // (col, value bits) pairs
-    for (int ch = 0; ch < nchunks; ch++) {
-      int w = 0;
-      for (int r = 64 * ch; r < std::min(N, 64 * ch + 64); r++) w = std::max(w, H.P_ptr[r + 1] - H.P_ptr[r]);
-      eptr[ch] = (int) (flat.size() / 2); ew[ch] = w;
-      flat.resize(flat.size() + (size_t) 2 * 64 * w);
-      for (int s = 0; s < w; s++)
-        for (int l = 0; l < 64; l++) {
-          const int r = 64 * ch + l;
-          int col = std::min(r, N - 1);
-          float val = 0.f;
-          if (r < N && H.P_ptr[r] + s < H.P_ptr[r + 1]) { col = H.P_col[H.P_ptr[r] + s]; val = (float) H.P_val[H.P_ptr[r] + s]; }
-          int bits;
-          std::memcpy(&bits, &val, sizeof(int));
-          const size_t o = 2 * ((size_t) eptr[ch] + (size_t) s * 64 + l);
-          flat[o] = col; flat[o + 1] = bits;
-        }
-    }
-    const int *ellp;
-    if ((rc = upload<int>(c, &ellp, flat))) return rc;
-    S.ell = (const int2 *) ellp;
-    if ((rc = upload<int>(c, &S.ell_ptr, eptr))) return rc;
-    if ((rc = upload<int>(c, &S.ell_w, ew))) return rc;
+  if (plan.pk_ok) {
+    if ((rc = upload_as<int>(c, &S.pk, plan.pk.pk))) return rc;
+    if ((rc = upload<int>(c, &S.pk_ptr, plan.pk.pk_ptr))) return rc;
+    if ((rc = upload<int>(c, &S.pk_n, plan.pk.pk_n))) return rc;
   }
-  {  // element windows: the local step and the adjoint's element pass run inside LDS
-    HostWindows HW;
-    const char *envw = getenv("DC_WINDOWS");       // development switch: DC_WINDOWS=0 keeps the global-memory corner passes
-    S.win_ok = 0;
-    if (!(envw && envw[0] == '0') && HW.build(H, (size_t) 150 * 1024)) {
-      const int *ip; const float *fp;
-      if ((rc = upload<int>(c, &ip, HW.win))) return rc;
-      S.win = (const int4 *) ip;
-      if ((rc = upload<int>(c, &ip, HW.tri_rec))) return rc;
-      S.wtri_rec = (const int4 *) ip;
-      if ((rc = upload<float>(c, &fp, HW.tri_D))) return rc;
-      S.wtri_D = (const float4 *) fp;
-      if ((rc = upload<int>(c, &ip, HW.bend_rec))) return rc;
-      S.wbend_rec = (const int4 *) ip;
-      if ((rc = upload<float>(c, &fp, HW.bend_w))) return rc;
-      S.wbend_w = (const float4 *) fp;
-      if ((rc = upload<float>(c, &fp, HW.tri_Dlo))) return rc;
-      S.wtri_Dlo = (const float4 *) fp;
-      if ((rc = upload<float>(c, &fp, HW.bend_lo))) return rc;
-      S.wbend_lo = (const float4 *) fp;
-      if ((rc = upload<int>(c, &ip, HW.inc))) return rc;
-      S.winc = (const int4 *) ip;
-      if ((rc = upload<int>(c, &S.winc_ptr, HW.inc_ptr))) return rc;
-      if ((rc = upload<int>(c, &S.winc_n, HW.inc_n))) return rc;
-      S.nwin = HW.nwin; S.win_vcap = HW.vcap; S.win_nrcap = HW.nrcap; S.win_lds_bytes = (int) HW.lds_bytes;
-      S.win_ok = 1;
-    }
+  if ((rc = upload<float>(c, &S.sq_dinv, plan.pk_ok ? plan.pk.sq_dinv : plan.sq_dinv))) return rc;
+  if (defl) {
+    if ((rc = upload<float>(c, &S.defl_u, HD->U))) return rc;
+    if ((rc = upload<float>(c, &S.defl_au, HD->AU))) return rc;
+    if ((rc = upload<float>(c, &S.defl_g, HD->G))) return rc;
   }
-  {  // packet-ELL copy of the scaled matrix for dc_forward_pk.hip (dc_packets.h)
-    HostPackets HP;
-    S.pk_ok = 0; S.pk_vpt = 0; S.pk = nullptr; S.pk_ptr = nullptr; S.pk_n = nullptr; S.sq_dinv = nullptr;
-    if (HP.build(H)) {
-      const int *pkp;
-      if ((rc = upload<int>(c, &pkp, HP.pk))) return rc;
-      S.pk = (const int4 *) pkp;
-      if ((rc = upload<int>(c, &S.pk_ptr, HP.pk_ptr))) return rc;
-      if ((rc = upload<int>(c, &S.pk_n, HP.pk_n))) return rc;
-      if ((rc = upload<float>(c, &S.sq_dinv, HP.sq_dinv))) return rc;
-      S.pk_vpt = HP.vpt; S.pk_threads = HP.threads; S.pk_ok = 1;
-    } else {
-      // no packet tables (matrix bandwidth beyond the +-511 of their column deltas: the reference's 17 562-vertex dress, 647 after
-      // renumbering): the scaling D^-1/2 alone, for the coarse level of the ADJOINT's preconditioner (dc_adjoint64.h), which such a mesh needs
-      std::vector<float> sq((size_t) round64(N), 0.f);
-      for (int r = 0; r < N; r++)
-        for (int k = H.P_ptr[r]; k < H.P_ptr[r + 1]; k++)
-          if (H.P_col[k] == r) sq[r] = (float) (1.0 / std::sqrt(H.P_val[k]));
-      if ((rc = upload<float>(c, &S.sq_dinv, sq))) return rc;
-    }
-  }
-  {  // irregular garments: the 16 lowest eigenvectors of the scaled matrix as a deflation space of the forward solve (dc_deflate.h)
-    HostDeflation *HDp = nullptr;
-    S.defl_u = nullptr; S.defl_au = nullptr; S.defl_g = nullptr; c->defl_k = 0; c->defl_probe = 0;
-    const int want = deflation_want(p);
-    // (the deflated FORWARD kernels exist for 512 threads x >= 4 rows: meshes of more than 1536 vertices, dc_forward_pk_defl.hip; smaller meshes
-    //  solve their forward step with the explicit inverse and use the space for the adjoint's coarse level only)
-    S.fwd_defl = 0;
-    if (S.win_ok && build_deflation_cached(c, H, want, S.pk_ok ? S.pk_threads * S.pk_vpt : round64(N), &HDp)) {
-      const HostDeflation &HD = *HDp;
-      if ((rc = upload<float>(c, &S.defl_u, HD.U))) return rc;
-      if ((rc = upload<float>(c, &S.defl_au, HD.AU))) return rc;
-      if ((rc = upload<float>(c, &S.defl_g, HD.G))) return rc;
-      c->defl_k = HD.k;
-      // (round 6: a mesh without packet tables runs the global-memory kernel, which projects too — dc_devlib.h: deflate_global)
-      S.fwd_defl = ((S.pk_ok && S.pk_threads == 512 && S.pk_vpt >= 4) || !S.pk_ok) ? 1 : 0;
-    }
-    static const char *envc = getenv("DC_ADJ_COARSE");      // development switch: 0 = block preconditioner only in the adjoint's fall-back
-    S.adj_coarse = (S.defl_u && !(envc && atoi(envc) == 0)) ? 1 : 0;
-    c->defl_probe = HDp ? HDp->probe_iterations : 0;
-  }
-  {  // small meshes: explicit inverse of the scaled matrix (dc_dense.h) for the forward global step
-    HostDense HD;
-    const char *envd = getenv("DC_DENSE_MAX_N");   // development switch: 0 disables, other values move the size limit
-    const int max_n = envd ? atoi(envd) : kDenseMaxN;   // 2.4 MB: the matrix must stay in every XCD's 4 MB L2 next to the other tables
-    S.dense_inv = nullptr; S.dense_ld = 0;
-    if (S.pk_ok && S.win_ok && HD.build(H, max_n)) {
-      if ((rc = upload<float>(c, &S.dense_inv, HD.inv))) return rc;
-      S.dense_ld = HD.ld;
-    }
-  }
+  if (plan.dense_ld && (rc = upload<float>(c, &S.dense_inv, plan.dense.inv))) return rc;
   S.h = (float) p.time_step; S.k_att = (float) p.k_att;
   S.k_stretch = (float) p.k_stretch; S.k_bend = (float) p.k_bend; S.density = (float) p.density;
   S.gx = p.gravity_enabled ? (float) p.gravity[0] : 0.f;
@@ -1241,10 +1087,7 @@ int dc_step_forward(dc_ctx *c, int slot, const double *fixed_pts, dc_step_stats 
     if ((rc = h2d_planar(c, fixed_pts, c->xf_cur, Af, 2, false))) return rc;
     c->sched_xf[slot + 1] = 0;               // explicit targets win over a schedule entry of this step
   }
-  if (Af > 0 && !c->sched_xf[slot + 1]) HIPCHK(c, hipMemcpyAsync(c->XF + (size_t) c->B * 3 * Af * (slot + 1), c->xf_cur, sizeof(float) * c->B * 3 * Af, hipMemcpyDeviceToDevice, c->stream));
-  if (c->S.contact_enabled && c->S.self_enabled) launch_self_detect(c->S, c->W, fwd_args(c, slot), c->B, c->stream);
-  if ((rc = cluster_begin(c))) return rc;
-  if ((rc = enqueue_pd_step(c, fwd_args(c, slot)))) return rc;
+  if ((rc = enqueue_forward_steps(c, slot, 1, false, nullptr))) return rc;
   if (stats) {
     HIPCHK(c, hipMemcpyAsync(stats, c->fstats + (size_t) c->B * (slot + 1), sizeof(dc_step_stats) * c->B, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1292,18 +1135,19 @@ int dc_get_self_contacts(dc_ctx *c, int slot, int rollout, int cap, int *count, 
   if (rc) return rc;
   if (slot < 1 || rollout < 0 || rollout >= c->B) return fail(c, DC_ERR_INVALID, "dc_get_self_contacts: bad slot / rollout");
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  const SelfRec R = self_slot(c, slot);
   std::vector<int> meta_v(kMetaStride); int *meta = meta_v.data();
-  HIPCHK(c, hipMemcpy(meta, c->SC_meta + ((size_t) c->B * slot + rollout) * kMetaStride, sizeof(int) * kMetaStride, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(meta, R.meta + (size_t) rollout * kMetaStride, sizeof(int) * kMetaStride, hipMemcpyDeviceToHost));
   const int C = meta[0], nl = meta[1];
   if (count) *count = C;
   if (num_layers) *num_layers = nl;
   const int n = std::min(C, cap);
   if (n <= 0) return DC_OK;
-  const size_t base = ((size_t) c->B * slot + rollout) * c->self_cap;
+  const size_t base = (size_t) rollout * c->self_cap;
   std::vector<int2> pr(n);
   std::vector<float4> nr(n);
-  HIPCHK(c, hipMemcpy(pr.data(), c->SC_pair + base, sizeof(int2) * n, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(nr.data(), c->SC_nrm + base, sizeof(float4) * n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(pr.data(), R.pair + base, sizeof(int2) * n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(nr.data(), R.nrm + base, sizeof(float4) * n, hipMemcpyDeviceToHost));
   for (int k = 0; k < n; k++) {
     if (pairs) {
       pairs[2 * k] = c->user_of.empty() ? pr[k].x : c->user_of[pr[k].x];
@@ -1354,7 +1198,7 @@ int dc_set_record(dc_ctx *c, int slot, const dc_record *rec) {
     HIPCHK(c, hipMemcpy(c->PRIM + sp * slot, prim.data(), sp * sizeof(int), hipMemcpyHostToDevice));
   }
   if (rec->x_fixed && Af > 0) {
-    if ((rc = h2d_planar(c, rec->x_fixed, c->XF + (size_t) B * 3 * Af * slot, Af, 2, false))) return rc;
+    if ((rc = h2d_planar(c, rec->x_fixed, xf_slot(c, slot), Af, 2, false))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   {  // self contacts: the record layout the detection kernel leaves (dc_selflib.h): contacts by layer, pairs in device numbering (.x = the
@@ -1401,12 +1245,12 @@ int dc_set_record(dc_ctx *c, int slot, const dc_record *rec) {
       }
       at += C;
     }
-    const size_t sc = (size_t) B * cap * slot;
-    HIPCHK(c, hipMemcpy(c->SC_meta + (size_t) B * kMetaStride * slot, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->SC_pair + sc, pair.data(), pair.size() * sizeof(int2), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->SC_nrm + sc, nrm.data(), nrm.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->SC_d + sc, dv.data(), dv.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->SC_verts + 2 * sc, verts.data(), verts.size() * sizeof(int), hipMemcpyHostToDevice));
+    const SelfRec R = self_slot(c, slot);
+    HIPCHK(c, hipMemcpy(R.meta, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(R.pair, pair.data(), pair.size() * sizeof(int2), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(R.nrm, nrm.data(), nrm.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(R.dvec, dv.data(), dv.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(R.verts, verts.data(), verts.size() * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->INJ_SN, sn.data(), sn.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->INJ_SD, sd.data(), sd.size() * sizeof(double), hipMemcpyHostToDevice));
   }
@@ -1431,8 +1275,7 @@ int dc_step_backward(dc_ctx *c, int slot, const double *dL_dxnew, const double *
     if ((rc = h2d_planar(c, dL_dvinit, c->IV, N, 3, true))) return rc;
   }
   HIPCHK(c, hipMemsetAsync(c->DMU, 0, sizeof(float) * c->B * G, c->stream));
-  if (Af > 0) HIPCHK(c, hipMemsetAsync(c->DXF + (size_t) c->B * 3 * Af * slot, 0, sizeof(float) * c->B * 3 * Af, c->stream));
-  if ((rc = cluster_begin(c))) return rc;
+  if (Af > 0) HIPCHK(c, hipMemsetAsync(dxf_slot(c, slot), 0, sizeof(float) * xf_elems(c), c->stream));
   {
     BwdArgs BA = bwd_args(c, slot, is_start != 0, with_init);
     if (!with_init) { BA.ix = nullptr; BA.iv = nullptr; BA.slot_ix = 0; }     // the per-step call takes its seeds from its arguments only
@@ -1440,7 +1283,7 @@ int dc_step_backward(dc_ctx *c, int slot, const double *dL_dxnew, const double *
   }
   if ((rc = d2h_planar(c, c->GX, dL_dx, N, 0, true))) return rc;
   if ((rc = d2h_planar(c, c->GV, dL_dv, N, 1, true))) return rc;
-  if (dL_dxfixed && Af > 0 && (rc = d2h_planar(c, c->DXF + (size_t) c->B * 3 * Af * slot, dL_dxfixed, Af, 2, false))) return rc;
+  if (dL_dxfixed && Af > 0 && (rc = d2h_planar(c, dxf_slot(c, slot), dL_dxfixed, Af, 2, false))) return rc;
   std::vector<float> dmu((size_t) c->B * G);
   HIPCHK(c, hipMemcpyAsync(dmu.data(), c->DMU, dmu.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   if (stats) HIPCHK(c, hipMemcpyAsync(stats, c->bstats + (size_t) c->B * slot, sizeof(dc_bwd_stats) * c->B, hipMemcpyDeviceToHost, c->stream));
@@ -1495,10 +1338,7 @@ int dc_step_forward_dev(dc_ctx *c, int slot, const void *d_fixed_pts, int is_f32
     launch_dev_to_planar(d_fixed_pts, is_f32, c->xf_cur, c->B, Af, nullptr, c->stream);
     c->sched_xf[slot + 1] = 0;
   }
-  if (Af > 0 && !c->sched_xf[slot + 1]) HIPCHK(c, hipMemcpyAsync(c->XF + (size_t) c->B * 3 * Af * (slot + 1), c->xf_cur, sizeof(float) * c->B * 3 * Af, hipMemcpyDeviceToDevice, c->stream));
-  if (c->S.contact_enabled && c->S.self_enabled) launch_self_detect(c->S, c->W, fwd_args(c, slot), c->B, c->stream);
-  if ((rc = cluster_begin(c))) return rc;
-  return enqueue_pd_step(c, fwd_args(c, slot));
+  return enqueue_forward_steps(c, slot, 1, false, nullptr);
 }
 
 int dc_step_backward_dev(dc_ctx *c, int slot, const void *d_dL_dxnew, const void *d_dL_dvnew, const void *d_dL_dxinit, const void *d_dL_dvinit,
@@ -1517,8 +1357,7 @@ int dc_step_backward_dev(dc_ctx *c, int slot, const void *d_dL_dxnew, const void
     launch_dev_to_planar(d_dL_dvinit, is_f32, c->IV, c->B, N, c->d_user_of, c->stream);
   }
   HIPCHK(c, hipMemsetAsync(c->DMU, 0, sizeof(float) * c->B * G, c->stream));
-  if (Af > 0) HIPCHK(c, hipMemsetAsync(c->DXF + (size_t) c->B * 3 * Af * slot, 0, sizeof(float) * c->B * 3 * Af, c->stream));
-  if ((rc = cluster_begin(c))) return rc;
+  if (Af > 0) HIPCHK(c, hipMemsetAsync(dxf_slot(c, slot), 0, sizeof(float) * xf_elems(c), c->stream));
   {
     BwdArgs BA = bwd_args(c, slot, is_start != 0, with_init);
     if (!with_init) { BA.ix = nullptr; BA.iv = nullptr; BA.slot_ix = 0; }
@@ -1526,7 +1365,7 @@ int dc_step_backward_dev(dc_ctx *c, int slot, const void *d_dL_dxnew, const void
   }
   launch_planar_to_dev(c->GX, d_dL_dx, is_f32, c->B, N, c->d_user_of, c->stream);
   launch_planar_to_dev(c->GV, d_dL_dv, is_f32, c->B, N, c->d_user_of, c->stream);
-  if (d_dL_dxfixed && Af > 0) launch_planar_to_dev(c->DXF + (size_t) c->B * 3 * Af * slot, d_dL_dxfixed, is_f32, c->B, Af, nullptr, c->stream);
+  if (d_dL_dxfixed && Af > 0) launch_planar_to_dev(dxf_slot(c, slot), d_dL_dxfixed, is_f32, c->B, Af, nullptr, c->stream);
   if (d_dL_dmu) launch_copy_cast(c->DMU, d_dL_dmu, is_f32, (long) c->B * G, c->stream);
   HIPCHK(c, hipGetLastError());
   return DC_OK;
@@ -1535,46 +1374,10 @@ int dc_step_backward_dev(dc_ctx *c, int slot, const void *d_dL_dxnew, const void
 int dc_rollout_forward(dc_ctx *c, int slot, int nsteps) {
   int rc = check_batch(c, slot, slot + nsteps);
   if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventRecord(c->ev_a, c->stream));
-  const bool self_on = c->S.contact_enabled && c->S.self_enabled;
-  static const bool fuse_ok = !(getenv("DC_FUSE_STEPS") && getenv("DC_FUSE_STEPS")[0] == '0');     // development switch
-  const bool fused = fuse_ok && nsteps > 1 && (use_cluster_fwd(c) || pd_step_fusable(c->S));
-  if ((rc = cluster_begin(c))) return rc;
-  if (fused) {
-    // all steps of a rollout run inside ONE launch (self-collision detection inlined per step), so a rollout never waits
-    // for the slowest rollout of the batch between steps
-    // a schedule (dc_set_*_schedule) has to cover all steps of a fused sweep or none of them
-    int nxf = 0, nfu = 0, nfvs = 0;
-    for (int k = 1; k <= nsteps; k++) { nxf += c->sched_xf[slot + k]; nfu += c->sched_fu[slot + k]; nfvs += c->sched_fvs[slot + k]; }
-    if ((nxf % nsteps) || (nfu % nsteps) || (nfvs % nsteps))
-      return fail(c, DC_ERR_INVALID, "dc_rollout_forward: a fixed-point / force schedule covers only part of the steps " + std::to_string(slot) + " .. " + std::to_string(slot + nsteps));
-    for (int k = 0; k < nsteps && c->S.Af > 0 && nxf == 0; k++)
-      HIPCHK(c, hipMemcpyAsync(c->XF + (size_t) c->B * 3 * c->S.Af * (slot + k + 1), c->xf_cur, sizeof(float) * c->B * 3 * c->S.Af, hipMemcpyDeviceToDevice, c->stream));
-    FwdArgs A = fwd_args(c, slot);           // (points x_fixed / fu / fv_scale at the first step's schedule entries)
-    if (nxf) A.slot_xfix = (size_t) c->B * 3 * c->S.Af;
-    if (nfu) A.slot_fu = (size_t) c->B * 3;
-    if (nfvs && A.fv_scale) A.slot_fvs = (size_t) c->B;
-    A.nsteps = nsteps; A.inline_detect = self_on ? 1 : 0;
-    if ((rc = enqueue_pd_step(c, A))) return rc;
-  } else {
-    for (int k = 0; k < nsteps; k++) {
-      if (c->S.Af > 0 && !c->sched_xf[slot + k + 1]) HIPCHK(c, hipMemcpyAsync(c->XF + (size_t) c->B * 3 * c->S.Af * (slot + k + 1), c->xf_cur, sizeof(float) * c->B * 3 * c->S.Af, hipMemcpyDeviceToDevice, c->stream));
-      if (self_on) launch_self_detect(c->S, c->W, fwd_args(c, slot + k), c->B, c->stream);
-      if ((rc = enqueue_pd_step(c, fwd_args(c, slot + k)))) return rc;
-    }
-  }
-  if (c->S.Af > 0 && c->sched_xf[slot + nsteps])      // later unscheduled steps continue from the last scheduled targets
-    HIPCHK(c, hipMemcpyAsync(c->xf_cur, c->XF + (size_t) c->B * 3 * c->S.Af * (slot + nsteps), sizeof(float) * c->B * 3 * c->S.Af, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(c->ev_b, c->stream));
-  HIPCHK(c, hipGetLastError());
-  // kernel-time accounting is resolved lazily in dc_kernel_times / dc_sync
-  HIPCHK(c, hipEventSynchronize(c->ev_b));
-  float ms = 0;
-  HIPCHK(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
-  const int chunks = use_cluster_fwd(c) ? (c->B + c->cl.nb - 1) / c->cl.nb : 1;
-  c->fwd_ms += ms; c->fwd_launches += (fused ? 1 : nsteps) * chunks;
-  return cluster_check(c);
+  if ((rc = kernel_time_begin(c))) return rc;
+  int launches = 0;
+  if ((rc = enqueue_forward_steps(c, slot, nsteps, true, &launches))) return rc;
+  return kernel_time_end(c, false, launches);
 }
 
 int dc_seed_gradient(dc_ctx *c, int slot, const double *target, double scale_x) {
@@ -1597,19 +1400,15 @@ int dc_rollout_backward(dc_ctx *c, int slot, int nsteps) {
   int rc = check_batch(c, slot - nsteps + 1, slot);
   if (rc) return rc;
   if (slot - nsteps + 1 < 1) return fail(c, DC_ERR_INVALID, "dc_rollout_backward: would run past slot 1");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventRecord(c->ev_a, c->stream));
-  static const bool fuse_ok = !(getenv("DC_FUSE_STEPS") && getenv("DC_FUSE_STEPS")[0] == '0');     // development switch
-  if ((rc = cluster_begin(c))) return rc;
+  if ((rc = kernel_time_begin(c))) return rc;
   if (c->SEEDX) {
     int ns = 0;
     for (int k = 0; k < nsteps; k++) ns += c->sched_seed[slot - k - 1];
     if (ns % nsteps) return fail(c, DC_ERR_INVALID, "dc_rollout_backward: the seed schedule covers only part of the slots " + std::to_string(slot - nsteps) + " .. " + std::to_string(slot - 1));
   }
-  if (c->S.Af > 0) HIPCHK(c, hipMemsetAsync(c->DXF + (size_t) c->B * 3 * c->S.Af * (slot - nsteps + 1), 0, sizeof(float) * c->B * 3 * c->S.Af * nsteps, c->stream));
+  if (c->S.Af > 0) HIPCHK(c, hipMemsetAsync(dxf_slot(c, slot - nsteps + 1), 0, sizeof(float) * xf_elems(c) * nsteps, c->stream));
   const bool inj_inside = c->inj_slot >= slot - nsteps + 1 && c->inj_slot <= slot;      // (dc_set_record: that step gets a launch of its own)
-  const bool fused_bwd = fuse_ok && nsteps > 1 && !inj_inside && c->params.adjoint_mode != 2;     // (mode 2: assemble -> factor -> step per step)
-  const int dense_before = c->dense_launches;
+  const bool fused_bwd = fuse_steps_enabled() && nsteps > 1 && !inj_inside && c->params.adjoint_mode != 2;     // (mode 2: assemble -> factor -> step per step)
   if (fused_bwd) {
     BwdArgs A = bwd_args(c, slot, slot == c->start_slot + 1, false);
     A.nsteps = nsteps;                       // the whole sweep of a rollout in one launch
@@ -1620,14 +1419,7 @@ int dc_rollout_backward(dc_ctx *c, int slot, int nsteps) {
       if ((rc = enqueue_adjoint_step(c, bwd_args(c, s, s == c->start_slot + 1, false)))) return rc;   // isStart: Simulation.cpp:3947
     }
   }
-  HIPCHK(c, hipEventRecord(c->ev_b, c->stream));
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventSynchronize(c->ev_b));
-  float ms = 0;
-  HIPCHK(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
-  const int chunks = use_cluster_bwd(c) ? (c->B + c->cl.nb - 1) / c->cl.nb : 1;
-  c->bwd_ms += ms; c->bwd_launches += c->params.adjoint_mode == 2 ? c->dense_launches - dense_before : (fused_bwd ? 1 : nsteps) * chunks;
-  return cluster_check(c);
+  return kernel_time_end(c, true, fused_bwd ? 1 : nsteps);
 }
 
 int dc_set_trajectory_start(dc_ctx *c, int start_slot) {
@@ -1661,9 +1453,9 @@ int dc_set_fixed_point_schedule(dc_ctx *c, int slot0, int nsteps, const double *
   const int Af = c->S.Af;
   if (Af <= 0) return DC_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  const size_t per = (size_t) c->B * 3 * Af;
+  const size_t per = xf_elems(c);
   for (int k = 0; k < nsteps; k++) {
-    if ((rc = h2d_planar(c, xf + per * k, c->XF + per * (slot0 + k + 1), Af, k & 3, false))) return rc;
+    if ((rc = h2d_planar(c, xf + per * k, xf_slot(c, slot0 + k + 1), Af, k & 3, false))) return rc;
     c->sched_xf[slot0 + k + 1] = 1;
     if ((k & 3) == 3) HIPCHK(c, hipStreamSynchronize(c->stream));      // the four staging buffers are reused
   }
@@ -1703,9 +1495,9 @@ int dc_set_seed_schedule(dc_ctx *c, int slot0, int nslots, const double *dL_dx, 
   }
   const int N = c->host.N;
   for (int k = 0; k < nslots; k++) {
-    if ((rc = h2d_planar(c, dL_dx + (size_t) 3 * N * c->B * k, c->SEEDX + se * (slot0 + k), N, 0, true))) return rc;
-    if (dL_dv) { if ((rc = h2d_planar(c, dL_dv + (size_t) 3 * N * c->B * k, c->SEEDV + se * (slot0 + k), N, 1, true))) return rc; }
-    else HIPCHK(c, hipMemsetAsync(c->SEEDV + se * (slot0 + k), 0, se * sizeof(float), c->stream));
+    if ((rc = h2d_planar(c, dL_dx + (size_t) 3 * N * c->B * k, seedx_slot(c, slot0 + k), N, 0, true))) return rc;
+    if (dL_dv) { if ((rc = h2d_planar(c, dL_dv + (size_t) 3 * N * c->B * k, seedv_slot(c, slot0 + k), N, 1, true))) return rc; }
+    else HIPCHK(c, hipMemsetAsync(seedv_slot(c, slot0 + k), 0, se * sizeof(float), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->sched_seed[slot0 + k] = 1;
   }
@@ -1752,9 +1544,9 @@ int dc_get_dxfixed(dc_ctx *c, int slot0, int nslots, double *dL_dxfixed) {
   const int Af = c->S.Af;
   if (Af <= 0) return DC_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  const size_t per = (size_t) c->B * 3 * Af;
+  const size_t per = xf_elems(c);
   for (int k = 0; k < nslots; k++) {
-    if ((rc = d2h_planar(c, c->DXF + per * (slot0 + k), dL_dxfixed + per * k, Af, 2, false))) return rc;
+    if ((rc = d2h_planar(c, dxf_slot(c, slot0 + k), dL_dxfixed + per * k, Af, 2, false))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   return DC_OK;
@@ -1766,7 +1558,7 @@ int dc_get_param_gradients(dc_ctx *c, int slot, double *out) {
   if (slot < 1 || !out) return fail(c, DC_ERR_INVALID, "dc_get_param_gradients: slot 0 has no record");
   HIPCHK(c, hipStreamSynchronize(c->stream));
   std::vector<float> v((size_t) c->B * 8);
-  HIPCHK(c, hipMemcpy(v.data(), c->DPAR + (size_t) c->B * 8 * slot, v.size() * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(v.data(), dpar_slot(c, slot), v.size() * sizeof(float), hipMemcpyDeviceToHost));
   for (size_t k = 0; k < v.size(); k++) out[k] = v[k];
   return DC_OK;
 }
@@ -1800,101 +1592,7 @@ int dc_get_layout(const dc_ctx *c, int *out6) {
   if (!c || !out6) return DC_ERR_INVALID;
   if (!c->built) return DC_ERR_STATE;
   out6[0] = c->user_of.empty() ? 0 : 1; out6[1] = c->bandwidth; out6[2] = c->S.pk_ok; out6[3] = c->S.win_ok; out6[4] = c->S.nwin;
-  out6[5] = c->S.dense_inv ? 1 : 0;
-  return DC_OK;
-}
-
-// ---- collective for C++ callers (the L-BFGS side sums loss + parameter gradients over the ranks) ------------------
-// RCCL is bound at run time (dlopen) the first time one of these entry points is used: the library has no link-time dependency on it,
-// and a process that already carries an RCCL (torch.distributed) gets that same copy by its soname.
-extern "C++" {
-namespace {
-struct RcclApi {
-  void *lib = nullptr;
-  ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
-  ncclResult_t (*CommInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
-  ncclResult_t (*AllReduce)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-  const char *(*GetErrorString)(ncclResult_t) = nullptr;
-  std::string error;
-};
-RcclApi &rccl() {
-  static RcclApi api;
-  if (api.lib || !api.error.empty()) return api;
-  for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-    api.lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-    if (api.lib) break;
-  }
-  if (!api.lib) {
-    const char *why = dlerror();      // (one call: dlerror() clears the message it returns)
-    api.error = std::string("RCCL not found (dlopen librccl.so.1): ") + (why ? why : "");
-    return api;
-  }
-  api.GetUniqueId = (decltype(api.GetUniqueId)) dlsym(api.lib, "ncclGetUniqueId");
-  api.CommInitRank = (decltype(api.CommInitRank)) dlsym(api.lib, "ncclCommInitRank");
-  api.AllReduce = (decltype(api.AllReduce)) dlsym(api.lib, "ncclAllReduce");
-  api.CommDestroy = (decltype(api.CommDestroy)) dlsym(api.lib, "ncclCommDestroy");
-  api.GetErrorString = (decltype(api.GetErrorString)) dlsym(api.lib, "ncclGetErrorString");
-  if (!api.GetUniqueId || !api.CommInitRank || !api.AllReduce || !api.CommDestroy) { api.error = "RCCL library lacks the expected entry points"; api.lib = nullptr; }
-  return api;
-}
-int rccl_fail(dc_ctx *c, const char *what, ncclResult_t r) {
-  RcclApi &R = rccl();
-  return fail(c, DC_ERR_HIP, std::string(what) + ": " + (R.GetErrorString ? R.GetErrorString(r) : "RCCL error") + " (" + std::to_string((int) r) + ")");
-}
-}  // namespace
-}  // extern "C++"
-
-int dc_comm_unique_id(char *id128) {
-  if (!id128) return DC_ERR_INVALID;
-  RcclApi &R = rccl();
-  if (!R.lib) return DC_ERR_HIP;
-  ncclUniqueId id;
-  if (R.GetUniqueId(&id) != ncclSuccess) return DC_ERR_HIP;
-  std::memcpy(id128, id.internal, NCCL_UNIQUE_ID_BYTES);
-  return DC_OK;
-}
-
-int dc_comm_init(dc_ctx *c, int nranks, int rank, const char *id128) {
-  if (!c || !id128 || nranks < 1 || rank < 0 || rank >= nranks) return fail(c, DC_ERR_INVALID, "dc_comm_init: bad arguments");
-  if (c->host_only) return fail(c, DC_ERR_STATE, "dc_comm_init: host-only context");
-  RcclApi &R = rccl();
-  if (!R.lib) return fail(c, DC_ERR_HIP, R.error);
-  if (c->comm) { int rc = dc_comm_destroy(c); if (rc) return rc; }
-  HIPCHK(c, hipSetDevice(c->device));
-  ncclUniqueId id;
-  std::memcpy(id.internal, id128, NCCL_UNIQUE_ID_BYTES);
-  ncclComm_t comm = nullptr;
-  ncclResult_t r = R.CommInitRank(&comm, nranks, id, rank);
-  if (r != ncclSuccess) return rccl_fail(c, "ncclCommInitRank", r);
-  c->comm = (void *) comm; c->comm_ranks = nranks;
-  return DC_OK;
-}
-
-int dc_allreduce_sum(dc_ctx *c, double *inout, int count) {
-  if (!c || !inout || count < 1) return fail(c, DC_ERR_INVALID, "dc_allreduce_sum: bad arguments");
-  if (!c->comm) return fail(c, DC_ERR_STATE, "dc_allreduce_sum: dc_comm_init has not been called");
-  RcclApi &R = rccl();
-  HIPCHK(c, hipSetDevice(c->device));
-  double *buf = nullptr;
-  HIPCHK(c, hipMalloc((void **) &buf, sizeof(double) * (size_t) count));
-  hipError_t e = hipMemcpyAsync(buf, inout, sizeof(double) * (size_t) count, hipMemcpyHostToDevice, c->stream);
-  ncclResult_t r = ncclSuccess;
-  if (e == hipSuccess) r = R.AllReduce(buf, buf, (size_t) count, ncclFloat64, ncclSum, (ncclComm_t) c->comm, c->stream);
-  if (e == hipSuccess && r == ncclSuccess) e = hipMemcpyAsync(inout, buf, sizeof(double) * (size_t) count, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void) hipFree(buf);
-  if (r != ncclSuccess) return rccl_fail(c, "ncclAllReduce", r);
-  HIPCHK(c, e);
-  return DC_OK;
-}
-
-int dc_comm_destroy(dc_ctx *c) {
-  if (!c) return DC_ERR_INVALID;
-  if (!c->comm) return DC_OK;
-  RcclApi &R = rccl();
-  if (R.lib) (void) R.CommDestroy((ncclComm_t) c->comm);
-  c->comm = nullptr; c->comm_ranks = 0;
+  out6[5] = c->S.dense_ld > 0 ? 1 : 0;
   return DC_OK;
 }
 

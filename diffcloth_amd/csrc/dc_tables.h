@@ -1,0 +1,59 @@
+// Host-side table plan of a context: every table dc_build uploads besides the plain HostSystem arrays, in exactly the layout the kernels
+// read (dc_device.h: DevSystem), and the kernel-set decisions that follow from them. Built from the HostSystem, the parameters and the
+// values of the development switches that gate tables; no device is needed, so a host-only context (dc_create(-1)) reports the decisions
+// of the same code a device context runs, and tests/native/host_tables_check.cpp checks the tables on the CPU.
+// The deflation space of the forward solve stays with the context (its cache survives rebuilds): the plan supplies the row padding of its
+// tables (defl_rows) and turns the outcome into fwd_defl / adj_coarse (set_deflation).
+#pragma once
+#include <vector>
+#include "../../include/diffcloth_hip.h"
+#include "dc_dense.h"
+#include "dc_packets.h"
+#include "dc_system.h"
+#include "dc_windows.h"
+
+namespace dc {
+
+constexpr size_t kWindowLdsBudget = (size_t) 150 * 1024;   // LDS the element windows of the one-workgroup kernels may take
+
+inline int round64(int v) { return (v + 63) / 64 * 64; }
+
+// values of the development switches dc_build reads (defaults: everything on)
+struct TableSwitches {
+  bool windows = true;      // DC_WINDOWS=0: no element windows, the global-memory corner passes
+  int dense_max_n = 0;      // DC_DENSE_MAX_N: largest mesh that gets the explicit inverse (0 disables)
+  bool self_lds = true;     // DC_SELF_LDS=0: layered self-contact passes through global memory
+  bool adj_coarse = true;   // DC_ADJ_COARSE=0: no coarse level over the deflation space in the adjoint's fall-back
+};
+
+struct HostTables {
+  // ---- decisions ----
+  int bandwidth = 0;                   // max |column - row| of P
+  int win_ok = 0, nwin = 0;            // element windows (win)
+  int pk_ok = 0, pk_vpt = 0, pk_threads = 0;   // packet matrix (pk): rows per thread and threads of its kernel, 0 when the tables are refused
+  int defl_rows = 0;                   // row padding of the deflation tables: the packet kernel's rows, or N rounded up to 64; 0 = no space wanted
+  int fwd_defl = 0, adj_coarse = 0;    // set_deflation
+  int dense_ld = 0;                    // explicit inverse (dense): its leading dimension, 0 = not built
+  int self_cap = 0, self_lds = 1;
+  float max_radii = 0.f;
+
+  // ---- tables ----
+  std::vector<int> tri_v, bend_v;      // [3][T], [4][E] planar vertex indices
+  std::vector<float> bend_nw;          // [E][2] (rest norm, weight^2)
+  std::vector<float> dinv;             // [N] 1 / P_ii
+  std::vector<int> att_of_vertex;      // [N] fixed-point index or -1
+  std::vector<double> tri_D64, bend_w64, bend_nw64;   // [4][T], [4][E], [2][E] planar fp64 rest-shape tables
+  std::vector<float> tri_Dlo, bend_lo; // [T][4], [E][4] value - fl32(value): inv_deltaUV; cotan weights 1..3 and the rest norm (.w)
+  std::vector<int> ell;                // wave-sliced ELL copy of P: (column, float bits) per entry; padding entries (min(row, N - 1), 0.0f)
+  std::vector<int> ell_ptr, ell_w;     // per 64-row chunk: first entry, width (its widest row)
+  std::vector<float> sq_dinv;          // without packet tables only: [round64(N)] sqrt(1 / P_ii) (with them: pk.sq_dinv)
+  HostWindows win;
+  HostPackets pk;
+  HostDense dense;
+
+  void build(const HostSystem &H, const dc_params &p, const TableSwitches &sw);
+  // `built`: the context has a deflation space for defl_rows rows
+  void set_deflation(bool built, const TableSwitches &sw);
+};
+
+}  // namespace dc

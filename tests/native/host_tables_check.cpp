@@ -1,6 +1,7 @@
 // Test harness (CPU): the host-side table builders of the HIP kernels, checked against the plain constraint system.
 //   g++ -O1 -std=c++17 -I diffcloth_amd/csrc tests/native/host_tables_check.cpp diffcloth_amd/csrc/dc_system.cpp \
-//       diffcloth_amd/csrc/dc_windows.cpp diffcloth_amd/csrc/dc_packets.cpp -o host_tables_check
+//       diffcloth_amd/csrc/dc_windows.cpp diffcloth_amd/csrc/dc_packets.cpp diffcloth_amd/csrc/dc_dense.cpp diffcloth_amd/csrc/dc_tables.cpp \
+//       -o host_tables_check
 // Prints one line per check and exits non-zero on the first failure (driven by tests/test_host_native.py).
 #include <algorithm>
 #include <cmath>
@@ -13,6 +14,7 @@
 #include "dc_packets.h"
 #include "dc_dense.h"
 #include "dc_system.h"
+#include "dc_tables.h"
 #include "dc_windows.h"
 
 using namespace dc;
@@ -199,6 +201,93 @@ static double regular_slot_fraction(const HostWindows &W) {
   return all ? (double) good / (double) all : 0.0;
 }
 
+static int asbits(float f) { int b; std::memcpy(&b, &f, 4); return b; }
+static std::vector<double> diagonal(const HostSystem &H) {
+  std::vector<double> d(H.N, 0.0);
+  for (int r = 0; r < H.N; r++)
+    for (int k = H.P_ptr[r]; k < H.P_ptr[r + 1]; k++) if (H.P_col[k] == r) d[r] = H.P_val[k];
+  return d;
+}
+// value = fl32(value) + low part, the low part itself rounded to fp32: two roundings, each relative 2^-24 -> relative 2^-47 of the value
+static bool split_ok(double x, float lo) { return std::fabs((double) (float) x + (double) lo - x) <= std::ldexp(std::fabs(x), -47); }
+
+// The table plan of a context (dc_tables.h) against the plain CSR / rest data of the HostSystem it was built from.
+static void check_tables(const HostSystem &H, bool expect_packets) {
+  dc_params prm;
+  std::memset(&prm, 0, sizeof(prm));
+  TableSwitches sw;
+  sw.dense_max_n = 768;
+  HostTables P;
+  P.build(H, prm, sw);
+  const int N = H.N, T = H.T, E = H.E;
+  // wave-sliced ELL copy of P: every CSR entry exactly once in its row's lane, bit-equal; every other slot (min(row, N - 1), 0.0f)
+  const int nchunks = (N + 63) / 64;
+  if ((int) P.ell_ptr.size() != nchunks || (int) P.ell_w.size() != nchunks) fail("tables: ELL chunk count");
+  size_t at = 0;
+  for (int ch = 0; ch < nchunks; ch++) {
+    int w = 0;
+    for (int r = 64 * ch; r < std::min(N, 64 * ch + 64); r++) w = std::max(w, H.P_ptr[r + 1] - H.P_ptr[r]);
+    if (P.ell_w[ch] != w || P.ell_ptr[ch] != (int) at) fail("tables: ELL width must be the chunk's widest row, chunks back to back");
+    if (P.ell.size() < 2 * (at + (size_t) 64 * w)) fail("tables: ELL table too short");
+    for (int l = 0; l < 64; l++) {
+      const int r = 64 * ch + l;
+      std::vector<char> used(r < N ? H.P_ptr[r + 1] - H.P_ptr[r] : 0, 0);
+      for (int s = 0; s < w; s++) {
+        const int col = P.ell[2 * (at + (size_t) s * 64 + l)], bits = P.ell[2 * (at + (size_t) s * 64 + l) + 1];
+        bool found = false;
+        for (size_t k = 0; k < used.size() && !found; k++)
+          if (!used[k] && H.P_col[H.P_ptr[r] + k] == col && asbits((float) H.P_val[H.P_ptr[r] + k]) == bits) { found = true; used[k] = 1; }
+        if (!found && (bits != 0 || col != std::min(r, N - 1))) fail("tables: ELL padding entry must be (min(row, N - 1), 0)");
+      }
+      for (char u : used) if (!u) fail("tables: a CSR entry of P is missing from the ELL table");
+    }
+    at += (size_t) 64 * w;
+  }
+  if (P.ell.size() != 2 * at) fail("tables: ELL table length");
+  // planar index / fp64 tables = the interleaved host tables transposed; fp32 low parts
+  if (P.tri_v.size() != 3 * (size_t) T || P.tri_D64.size() != 4 * (size_t) T || P.tri_Dlo.size() != 4 * (size_t) T) fail("tables: triangle table sizes");
+  if (P.bend_v.size() != 4 * (size_t) E || P.bend_w64.size() != 4 * (size_t) E || P.bend_nw64.size() != 2 * (size_t) E || P.bend_nw.size() != 2 * (size_t) E ||
+      P.bend_lo.size() != 4 * (size_t) E) fail("tables: flap table sizes");
+  for (int t = 0; t < T; t++) {
+    for (int k = 0; k < 3; k++) if (P.tri_v[(size_t) k * T + t] != H.tri[3 * t + k]) fail("tables: planar triangle vertices");
+    for (int k = 0; k < 4; k++) {
+      if (P.tri_D64[(size_t) k * T + t] != H.tri_D[4 * t + k]) fail("tables: planar fp64 inv_deltaUV");
+      if (!split_ok(H.tri_D[4 * t + k], P.tri_Dlo[4 * t + k])) fail("tables: low part of inv_deltaUV");
+    }
+  }
+  for (int e = 0; e < E; e++) {
+    for (int k = 0; k < 4; k++) {
+      if (P.bend_v[(size_t) k * E + e] != H.bend_v[4 * e + k]) fail("tables: planar flap vertices");
+      if (P.bend_w64[(size_t) k * E + e] != H.bend_w[4 * e + k]) fail("tables: planar fp64 cotan weights");
+      if (k >= 1 && !split_ok(H.bend_w[4 * e + k], P.bend_lo[4 * e + k - 1])) fail("tables: low part of the cotan weights 1..3");
+    }
+    if (!split_ok(H.bend_n[e], P.bend_lo[4 * e + 3])) fail("tables: low part of the rest norm (.w)");
+    if (P.bend_nw64[e] != H.bend_n[e] || P.bend_nw64[(size_t) E + e] != H.bend_w2[e]) fail("tables: planar fp64 rest norm / weight");
+    if (P.bend_nw[2 * e] != (float) H.bend_n[e] || P.bend_nw[2 * e + 1] != (float) H.bend_w2[e]) fail("tables: fp32 rest norm / weight pairs");
+  }
+  // 1 / P_ii; without packet tables D^-1/2 on round64(N) rows (with them the scaling is the packet builder's, check_packets)
+  const std::vector<double> d = diagonal(H);
+  if ((int) P.dinv.size() != N || (int) P.att_of_vertex.size() != N) fail("tables: per-vertex table sizes");
+  for (int r = 0; r < N; r++) if (P.dinv[r] != (float) (1.0 / d[r])) fail("tables: dinv");
+  for (int r = 0; r < N; r++) {
+    const auto a = std::find(H.att_vertex.begin(), H.att_vertex.end(), r);
+    if (P.att_of_vertex[r] != (a == H.att_vertex.end() ? -1 : (int) (a - H.att_vertex.begin()))) fail("tables: att_of_vertex");
+  }
+  if (P.pk_ok != (expect_packets ? 1 : 0)) fail("tables: packet decision");
+  if (expect_packets) {
+    if (!P.sq_dinv.empty() || P.pk_vpt != P.pk.vpt || P.pk_threads != P.pk.threads || P.defl_rows != P.pk.vpt * P.pk.threads) fail("tables: packet decisions");
+  } else {
+    if ((int) P.sq_dinv.size() != (N + 63) / 64 * 64 || P.pk_vpt != 0 || P.pk_threads != 0 || P.dense_ld != 0) fail("tables: decisions without packet tables");
+    for (size_t r = 0; r < P.sq_dinv.size(); r++)
+      if (P.sq_dinv[r] != ((int) r < N ? (float) (1.0 / std::sqrt(d[r])) : 0.f)) fail("tables: sq_dinv fall-back");
+  }
+  int bw = 0;
+  for (int r = 0; r < N; r++) for (int k = H.P_ptr[r]; k < H.P_ptr[r + 1]; k++) bw = std::max(bw, std::abs(H.P_col[k] - r));
+  if (P.bandwidth != bw || P.win_ok != 1 || P.nwin != P.win.nwin || P.self_cap != std::max(2048, N) || P.self_lds != 1) fail("tables: decisions");
+  if ((P.dense_ld != 0) != (expect_packets && N <= 768) || P.dense_ld != (P.dense_ld ? P.dense.ld : 0)) fail("tables: explicit-inverse decision");
+  std::printf("ok tables N=%d chunks=%d ell=%zu pk_ok=%d dense_ld=%d\n", N, nchunks, at, P.pk_ok, P.dense_ld);
+}
+
 int main() {
   std::vector<double> pos;
   std::vector<int> tri;
@@ -241,6 +330,16 @@ int main() {
   HostPackets P3;
   if (P3.build(H3)) fail("packets: a bandwidth > 511 must be refused");
   std::printf("ok refusal bandwidth=%d\n", P3.bandwidth);
+  check_tables(H3, false);          // ... with the D^-1/2 scaling alone
+  // 3b. the table plan on grid cloths with vertex counts on both sides of the 64-row ELL chunk: 4, 63, 64, 65, 130
+  for (const auto &g : {std::pair<int, int>{2, 2}, {7, 9}, {8, 8}, {5, 13}, {10, 13}}) {
+    grid(g.first, g.second, false, pos, tri);
+    HostSystem Hg;
+    if (!Hg.set_mesh(g.first * g.second, pos.data(), (int) tri.size() / 3, tri.data())) fail("set_mesh (small grid)");
+    Hg.att_vertex = {0, Hg.N - 1};
+    if (!Hg.build_numerics(1.0 / 120, 0.3, 200.0, 0.02, 1e4)) fail("build_numerics (small grid)");
+    check_tables(Hg, true);
+  }
   // 4. explicit inverse of the scaled matrix of a small mesh (dc_dense.h): symmetric, zero padded, Ahat * inv = I to fp32
   {
     grid(24, 20, false, pos, tri);

@@ -94,6 +94,46 @@ def test_smallest_meshes_match_the_oracle(shape):
     assert np.linalg.norm(gb["dL_dv"][0] - rb["dL_dv"]) <= 1e-4 * np.linalg.norm(rb["dL_dv"])
 
 
+def _cloth_4():
+    V, F = meshes.grid_cloth(2, 2, 1.0, 1.0, "DOWN")
+    return f32(V), F, [], dict(time_step=1 / 120, density=0.3, k_stretch=150.0, k_bend=0.05)
+
+
+def _cloth_1600():
+    V, F = meshes.grid_cloth(40, 40, 4.5, 4.5, "DOWN")
+    return f32(V), F, [0, 39], dict(time_step=1 / 120, density=0.3, k_stretch=150.0, k_bend=0.05)
+
+
+def _hat():
+    import scenes
+    V, F = scenes.load_mesh("hat")
+    P, _, _ = scenes.normalise_model(V, scenes.HAT["orientation"], scenes.HAT["cloth_dim"])
+    return P, F, scenes.HAT["attachments"], dict(time_step=scenes.HAT["h"], density=scenes.HAT["density"], k_stretch=scenes.HAT["k_stretch"],
+                                                  k_bend=scenes.HAT["k_bend"])
+
+
+@pytest.mark.parametrize("mesh,expect", [
+    (_cloth_4, dict(packet_kernel=True, dense_inverse=True, vectors=0)),        # explicit inverse, one row per thread
+    (_cloth_1600, dict(packet_kernel=True, dense_inverse=False, vectors=0)),    # above the 768-vertex dense limit: packets, 4 rows per thread
+    (_hat, dict(packet_kernel=True, dense_inverse=True, vectors=16)),           # deflation space built, forward on the explicit inverse
+])
+def test_host_only_context_reports_the_kernel_set_of_a_device_context(mesh, expect):
+    """dc_get_layout / dc_get_deflation of a host-only context (what tests/test_host_tables.py asserts without a GPU) are the decisions of the
+    same table plan a device context uploads (csrc/dc_tables.h): for the same inputs both report the same kernel set."""
+    V, F, att, par = mesh()
+    got = []
+    for device in (-1, 0):
+        e = capi.Engine(device)
+        e.set_mesh(V, F); e.set_attachments(list(att)); e.set_params(**par); e.set_primitives([])
+        e.build()
+        got.append((e.layout(), e.deflation()))
+    print(got)
+    assert got[0] == got[1]
+    lay, defl = got[1]
+    assert lay["element_windows"] and lay["windows"] >= 1
+    assert lay["packet_kernel"] == expect["packet_kernel"] and lay["dense_inverse"] == expect["dense_inverse"] and defl[0] == expect["vectors"]
+
+
 def test_rest_state_without_forces_is_a_fixed_point():
     """No gravity, no contact, zero velocity, rest shape: the step must return the input exactly after one PD iteration, and
     the backward step of a zero gradient is zero."""
