@@ -70,15 +70,16 @@ struct dc_ctx {
   void *comm = nullptr;             // RCCL communicator of dc_comm_init (ncclComm_t), one rank per context
   int comm_ranks = 0;
   std::vector<void *> sched_pool;
-  // record handed in from outside (dc_set_record): fp64 values of x_new, f, primitive-contact normals [B][3][N], self-contact normals / d
-  // [B][cap][3]; allocated on first use, valid for tape slot inj_slot only (-1 = none)
   float *YS = nullptr;              // [(tape+1)][B][3][N] y of every backward step (dc_keep_force_gradients), allocated on first use
   bool keep_y = false;
+  // record handed in from outside (dc_set_record): fp64 values of x_new, f, primitive-contact normals [B][3][N], self-contact normals / d
+  // [B][cap][3]; allocated on first use, valid for tape slot inj_slot only (-1 = none)
   double *INJ_X = nullptr, *INJ_F = nullptr, *INJ_N = nullptr, *INJ_SN = nullptr, *INJ_SD = nullptr;
   int inj_slot = -1;
   dc_step_stats *fstats = nullptr;  // [(tape+1)][B]
   dc_bwd_stats *bstats = nullptr;   // [(tape+1)][B], indexed by the slot whose record was differentiated
-  double *stage[4] = {nullptr, nullptr, nullptr, nullptr};
+  double *stage[4] = {nullptr, nullptr, nullptr, nullptr};   // staging of the host <-> device conversions, handed out by stage_take (dc_engine.hip)
+  int stage_live = 0;               // how many of them have been handed out since the stream was last synchronised by stage_sync
   size_t stage_elems = 0;
   hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
   float fwd_ms = 0, bwd_ms = 0;

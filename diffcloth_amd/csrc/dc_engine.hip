@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 #include "dc_context.h"
+#include "dc_record.h"
 #include "dc_tables.h"
 #include "dc_spheremesh.h"
 #include "dc_selftmp.h"
@@ -19,7 +20,19 @@ hipError_t launch_pd_step_cluster(const DevSystem &S, const DevCluster &CL, cons
 hipError_t launch_adjoint_step_cluster(const DevSystem &S, const DevCluster &CL, const DevWork &W, const BwdArgs &A, int b0, int nb, hipStream_t st);
 }
 
+static_assert(rec::kMetaStride == kMetaStride && rec::kMaxLayers == kMaxLayers, "dc_record.h restates dc_device.h's record sizes");
+static_assert(sizeof(rec::Int2) == sizeof(int2) && alignof(rec::Int2) == alignof(int2), "dc_record.h: Int2 is uploaded as int2");
+static_assert(sizeof(rec::Float4) == sizeof(float4) && alignof(rec::Float4) == alignof(float4), "dc_record.h: Float4 is uploaded as float4");
+
 namespace {
+
+// The development switches of this file, one spelling per parse rule (DESIGN.md section 1 lists every switch with its rule, default and
+// the time it is read). env_on: only a value that starts with 1 enables; env_not_off: any value that does not start with 0 enables;
+// both give dflt when the variable is not set. env_int: atoi of the value.
+bool env_set(const char *name) { return getenv(name) != nullptr; }
+bool env_on(const char *name, bool dflt) { const char *e = getenv(name); return e ? e[0] == '1' : dflt; }
+bool env_not_off(const char *name, bool dflt) { const char *e = getenv(name); return e ? e[0] != '0' : dflt; }
+int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
 
 template <typename T>
 int dev_alloc(dc_ctx *c, std::vector<void *> &pool, T **out, size_t count) {
@@ -73,17 +86,36 @@ int pd_cap(const dc_ctx *c) {
   return (int) ((-std::log10(c->params.forward_tol)) * 150);   // Simulation.cpp:1182
 }
 
-// per_vertex: the array is indexed by vertex (the device renumbering applies); false: by attachment / other index
-int h2d_planar(dc_ctx *c, const double *src, float *dst, int n_per_rollout, int which_stage, bool per_vertex) {
-  size_t elems = (size_t) c->B * 3 * n_per_rollout;
-  HIPCHK(c, hipMemcpyAsync(c->stage[which_stage], src, elems * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  launch_f64i_to_f32p(c->stage[which_stage], dst, c->B, n_per_rollout, per_vertex ? c->d_user_of : nullptr, c->stream);
+// The staging buffers of the host <-> device conversions are handed out in turn; one that has been handed out since the last stage_sync is
+// not handed out again before the stream has been synchronised. Entry points end their staged copies with stage_sync: a host-to-device copy
+// has completed when the call returns (the caller may reuse its buffer), a device-to-host result is complete before the host touches it.
+int stage_sync(dc_ctx *c) {
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->stage_live = 0;
   return DC_OK;
 }
-int d2h_planar(dc_ctx *c, const float *src, double *dst, int n_per_rollout, int which_stage, bool per_vertex) {
+int stage_take(dc_ctx *c, double **buf) {
+  if (c->stage_live == 4) { const int rc = stage_sync(c); if (rc) return rc; }
+  *buf = c->stage[c->stage_live++];
+  return DC_OK;
+}
+// per_vertex: the array is indexed by vertex (the device renumbering applies); false: by attachment / other index
+int h2d_planar(dc_ctx *c, const double *src, float *dst, int n_per_rollout, bool per_vertex) {
   size_t elems = (size_t) c->B * 3 * n_per_rollout;
-  launch_f32p_to_f64i(src, c->stage[which_stage], c->B, n_per_rollout, per_vertex ? c->d_user_of : nullptr, c->stream);
-  HIPCHK(c, hipMemcpyAsync(dst, c->stage[which_stage], elems * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  double *stage;
+  int rc = stage_take(c, &stage);
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(stage, src, elems * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  launch_f64i_to_f32p(stage, dst, c->B, n_per_rollout, per_vertex ? c->d_user_of : nullptr, c->stream);
+  return DC_OK;
+}
+int d2h_planar(dc_ctx *c, const float *src, double *dst, int n_per_rollout, bool per_vertex) {
+  size_t elems = (size_t) c->B * 3 * n_per_rollout;
+  double *stage;
+  int rc = stage_take(c, &stage);
+  if (rc) return rc;
+  launch_f32p_to_f64i(src, stage, c->B, n_per_rollout, per_vertex ? c->d_user_of : nullptr, c->stream);
+  HIPCHK(c, hipMemcpyAsync(dst, stage, elems * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   return DC_OK;
 }
 
@@ -126,24 +158,26 @@ FwdArgs fwd_args(dc_ctx *c, int slot) {
   A.pd_cap = pd_cap(c);
   A.cg_max = c->params.cg_max_iter > 0 ? c->params.cg_max_iter : 500;
   A.stall_window = c->params.stall_window > 0 ? c->params.stall_window : 0x7fffffff;   // off by default: reference semantics
-  static const bool seed_on = !(getenv("DC_CG_SEED") && getenv("DC_CG_SEED")[0] == '0');     // development switch
+  static const bool seed_on = env_not_off("DC_CG_SEED", true);     // development switch
   A.cg_seed = seed_on ? 1 : 0;
-  { const char *envp = getenv("DC_FWD_SELFFULL"); A.self_full = envp ? (envp[0] == '1') : 0; }
+  A.self_full = env_on("DC_FWD_SELFFULL", false);
   A.nsteps = 1; A.inline_detect = 0; A.slot_state = se; A.slot_prim = sp; A.slot_stats = (size_t) c->B;
   A.slot_self = (size_t) c->B * c->self_cap; A.slot_meta = (size_t) c->B * kMetaStride;
   return A;
 }
-BwdArgs bwd_args(dc_ctx *c, int slot, bool is_start, bool with_init) {
+// where a backward step takes the loss gradient w.r.t. the state it started from: nowhere, the caller's init gradients (IX / IV), or the
+// seed schedule's entry of that state, when there is one (dc_set_seed_schedule)
+enum class Seeds { none, init, schedule };
+BwdArgs bwd_args(dc_ctx *c, int slot, bool is_start, Seeds seeds) {
   const size_t se = slot_elems(c), sp = (size_t) c->B * c->host.N;
   BwdArgs A;
   A.x_new = c->X + se * slot; A.rec_f = c->F + se * slot; A.rec_n = c->NRM + se * slot;
   A.rec_prim = c->PRIM + sp * slot; A.mu = c->mu;
   A.self = self_slot(c, slot);
   A.gx = c->GX; A.gv = c->GV;
-  A.ix = with_init ? c->IX : nullptr; A.iv = with_init ? c->IV : nullptr; A.slot_ix = 0;
-  if (!with_init && c->SEEDX && c->sched_seed[slot - 1]) {      // seed schedule: the loss gradient w.r.t. the state this step started from
-    A.ix = seedx_slot(c, slot - 1); A.iv = seedv_slot(c, slot - 1); A.slot_ix = se;
-  }
+  A.ix = nullptr; A.iv = nullptr; A.slot_ix = 0;
+  if (seeds == Seeds::init) { A.ix = c->IX; A.iv = c->IV; }
+  if (seeds == Seeds::schedule && c->SEEDX && c->sched_seed[slot - 1]) { A.ix = seedx_slot(c, slot - 1); A.iv = seedv_slot(c, slot - 1); A.slot_ix = se; }
   A.d_xfixed = dxf_slot(c, slot); A.d_mu = c->DMU;
   A.d_param = dpar_slot(c, slot);
   A.x_fixed = xf_slot(c, slot);
@@ -158,12 +192,12 @@ BwdArgs bwd_args(dc_ctx *c, int slot, bool is_start, bool with_init) {
   A.mode = c->params.adjoint_mode;
   A.rel_tol = (float) (c->params.adjoint_rel_tol > 0 ? c->params.adjoint_rel_tol : 1e-6);
   A.stall_window = c->params.stall_window > 0 ? c->params.stall_window : 0x7fffffff;   // off by default: reference semantics
-  { const char *envp = getenv("DC_BLOCK_PRE"); A.block_pre = envp ? (envp[0] != '0') : (c->params.adjoint_block_precond != 0); }   // (development switch)
-  { const char *envp = getenv("DC_ADJ_FP32"); A.fp32_only = envp ? (envp[0] == '1') : (c->params.adjoint_fp32_only != 0); }     // (development switch)
-  { const char *envp = getenv("DC_ADJ_DENSEY"); A.dense_y = envp ? (envp[0] == '1') : 0; }
-  { const char *envp = getenv("DC_ADJ_VERIFY"); A.verify_all = envp ? (envp[0] == '1') : 0; }     // (development switch)
-  { const char *envp = getenv("DC_ADJ_WARM"); A.warm = envp ? (envp[0] == '1') : 0; }            // (development switch)
-  { const char *envp = getenv("DC_ADJ_CG"); A.cg_first = envp ? (envp[0] == '1') : 1; }          // (A/B switch: 0 = BiCGSTAB correction solves only)
+  A.block_pre = env_not_off("DC_BLOCK_PRE", c->params.adjoint_block_precond != 0);     // (development switches)
+  A.fp32_only = env_on("DC_ADJ_FP32", c->params.adjoint_fp32_only != 0);
+  A.dense_y = env_on("DC_ADJ_DENSEY", false);
+  A.verify_all = env_on("DC_ADJ_VERIFY", false);
+  A.warm = env_on("DC_ADJ_WARM", false);
+  A.cg_first = env_on("DC_ADJ_CG", true);                                                     // (A/B switch: 0 = BiCGSTAB correction solves only)
   A.ycap = 0; A.ybase = 0;                                                                                    // (set by the launch, dc_adjoint.hip)
   A.nsteps = 1; A.slot = slot;
   const bool inj = c->inj_slot == slot && c->INJ_X;
@@ -244,10 +278,10 @@ int build_cluster(dc_ctx *c, int K, bool forced) {
   std::memset(&D, 0, sizeof(D));
   D.K = K; D.R = R; D.HB = HB; D.wpp = wpp; D.xch_stride = kXchWaves + 2 * HB; D.pk_vpt = vpt;
   D.spin_limit = kSpinLimit; D.test_drop = 0; D.test_skew = -1;
-  { const char *ev = getenv("DC_SELF_REDUNDANT"); D.redundant_self = ev ? (ev[0] == '1') : 1; }
-  if (const char *ev = getenv("DC_TEST_SPIN_MS")) { const long long ms = atoll(ev); if (ms > 0) D.spin_limit = ms * 100000ll; }      // test hooks
-  if (const char *ev = getenv("DC_TEST_DROP_PART")) D.test_drop = ev[0] == '1';
-  if (const char *ev = getenv("DC_TEST_SKEW_PART")) D.test_skew = atoi(ev);
+  D.redundant_self = env_on("DC_SELF_REDUNDANT", true);
+  { const long long ms = env_int("DC_TEST_SPIN_MS", 0); if (ms > 0) D.spin_limit = ms * 100000ll; }      // test hooks
+  D.test_drop = env_on("DC_TEST_DROP_PART", false);
+  D.test_skew = env_int("DC_TEST_SKEW_PART", -1);
   int rc;
   const int *ip; const float *fp;
   if ((rc = upload_cl<int>(c, &ip, HW.win))) return rc;
@@ -295,8 +329,7 @@ int build_cluster(dc_ctx *c, int K, bool forced) {
 // Which deflation space the forward solve wants (dc_params::forward_deflation: -1 decide by the probe solve, 0 never, > 0 always; the
 // development switch DC_DEFLATION overrides it: 0 = off, 1 = always) — one rule for device and host-only contexts, read at every build.
 static int deflation_want(const dc_params &p) {
-  const char *envd = getenv("DC_DEFLATION");
-  if (envd) return atoi(envd) > 0 ? 16 : 0;
+  if (env_set("DC_DEFLATION")) return env_int("DC_DEFLATION", 0) > 0 ? 16 : 0;
   return p.forward_deflation > 0 ? 16 : p.forward_deflation;
 }
 // HostDeflation::build through the context's cache (key: the scalar system matrix, the request, the padded row count)
@@ -326,8 +359,7 @@ static void set_decisions(DevSystem &S, const HostTables &plan) {
 int choose_cluster(dc_ctx *c) {
   free_cluster(c);
   if (c->host_only || c->B <= 0) return DC_OK;
-  const char *env = getenv("DC_CLUSTER");
-  const int forced = env ? atoi(env) : -1;
+  const int forced = env_int("DC_CLUSTER", -1);
   if (forced == 0 || forced == 1) return DC_OK;
   if (c->S.dense_inv) { if (forced < 2) return DC_OK; }     // small meshes: the explicit-inverse kernels are the faster ones
   // Fewer rollouts than CUs: as many parts as fit (B K <= CUs), up to 8 — a rollout's speed-up grows with K (measured on C4: 1.3 /
@@ -393,8 +425,8 @@ int dense_ensure(dc_ctx *c) {
                      (size_t) 9 * cap * sizeof(double);
   const size_t budget = (size_t) 8 << 30;
   int nb = (int) std::max<size_t>(1, std::min<size_t>((size_t) c->B, budget / per));
-  const char *env = getenv("DC_DENSE_CHUNK");
-  if (env && atoi(env) > 0) nb = std::min(nb, atoi(env));
+  const int chunk = env_int("DC_DENSE_CHUNK", 0);
+  if (chunk > 0) nb = std::min(nb, chunk);
   int rc;
   DenseAdjWork &D = c->dense;
   D.ld = ld;
@@ -404,8 +436,7 @@ int dense_ensure(dc_ctx *c) {
   if ((rc = dev_alloc(c, c->batch_allocs, &D.pm, (size_t) nb * 9 * N))) return rc;
   if ((rc = dev_alloc(c, c->batch_allocs, &D.sg, (size_t) nb * 9 * cap))) return rc;
   c->dense_nb = nb;
-  const char *envt = getenv("DC_DENSE_TIMES");
-  c->dense_timing = envt && envt[0] == '1';
+  c->dense_timing = env_on("DC_DENSE_TIMES", false);
   if (c->dense_timing)
     for (auto &e : c->ev_d) if (!e) HIPCHK(c, hipEventCreate(&e));
   return DC_OK;
@@ -419,8 +450,7 @@ int enqueue_dense_adjoint(dc_ctx *c, const BwdArgs &A) {
   const DenseAdjWork &D = c->dense;
   const int n = 3 * c->host.N;
   static const int one = 1;
-  const char *envf = getenv("DC_DENSE_FLAG");
-  const int forced = (envf && envf[0] >= '0' && envf[0] <= '9') ? atoi(envf) : -1;
+  const int forced = env_int("DC_DENSE_FLAG", -1);
   for (int b0 = 0; b0 < c->B; b0 += c->dense_nb) {
     const int nb = std::min(c->dense_nb, c->B - b0);
     if (c->dense_timing) HIPCHK(c, hipEventRecord(c->ev_d[0], c->stream));
@@ -470,7 +500,7 @@ int enqueue_adjoint_step(dc_ctx *c, const BwdArgs &A) {
 
 // DC_FUSE_STEPS=0 (development switch, read once per process): one launch per step in dc_rollout_forward / dc_rollout_backward
 bool fuse_steps_enabled() {
-  static const bool on = !(getenv("DC_FUSE_STEPS") && getenv("DC_FUSE_STEPS")[0] == '0');
+  static const bool on = env_not_off("DC_FUSE_STEPS", true);
   return on;
 }
 
@@ -505,6 +535,37 @@ int enqueue_forward_steps(dc_ctx *c, int slot, int nsteps, bool carry_targets, i
   if (fused && (rc = enqueue_pd_step(c, FA))) return rc;
   if (carry_targets && has_xf && c->sched_xf[slot + nsteps])
     HIPCHK(c, hipMemcpyAsync(c->xf_cur, xf_slot(c, slot + nsteps), xf_bytes, hipMemcpyDeviceToDevice, c->stream));
+  if (launches) *launches = fused ? 1 : nsteps;
+  return DC_OK;
+}
+
+// The backward steps through the records slot, slot - 1 ... slot - nsteps + 1, enqueued on the context's stream: dL_dxfixed of those slots is
+// zeroed (the kernels add to it; DMU is the caller's: the per-step calls zero it, a sweep accumulates into what dc_seed_gradient / dc_set_gradient
+// zeroed), then one launch per step or, fused, the whole sweep of a rollout in ONE launch. A record handed in from outside (dc_set_record) gets
+// a launch of its own, and so does every step of adjoint_mode 2 (assemble -> factor -> step). seeds: where the steps take the loss gradient
+// w.r.t. the state they started from (the rollout call: the seed schedule, which has to cover all steps of the sweep or none; the per-step
+// calls: their init gradients or nothing). is_start: null = the step that started from the trajectory's initial state (isStart,
+// Simulation.cpp:3947). Returns the number of step-kernel launches per chunk of rollouts in *launches.
+int enqueue_backward_steps(dc_ctx *c, int slot, int nsteps, Seeds seeds, const bool *is_start, int *launches) {
+  const int first = slot - nsteps + 1;
+  int rc;
+  if (seeds == Seeds::schedule && c->SEEDX) {
+    int ns = 0;
+    for (int s = first; s <= slot; s++) ns += c->sched_seed[s - 1];
+    if (ns % nsteps) return fail(c, DC_ERR_INVALID, "dc_rollout_backward: the seed schedule covers only part of the slots " + std::to_string(first - 1) + " .. " + std::to_string(slot - 1));
+  }
+  if (c->S.Af > 0) HIPCHK(c, hipMemsetAsync(dxf_slot(c, first), 0, sizeof(float) * xf_elems(c) * nsteps, c->stream));
+  const bool inj_inside = c->inj_slot >= first && c->inj_slot <= slot;
+  const bool fused = fuse_steps_enabled() && nsteps > 1 && !inj_inside && c->params.adjoint_mode != 2;
+  auto start_of = [&](int s) { return is_start ? *is_start : s == c->start_slot + 1; };
+  if (fused) {
+    BwdArgs A = bwd_args(c, slot, start_of(slot), seeds);
+    A.nsteps = nsteps;
+    if ((rc = enqueue_adjoint_step(c, A))) return rc;
+  } else {
+    for (int s = slot; s >= first; s--)
+      if ((rc = enqueue_adjoint_step(c, bwd_args(c, s, start_of(s), seeds)))) return rc;
+  }
   if (launches) *launches = fused ? 1 : nsteps;
   return DC_OK;
 }
@@ -605,8 +666,8 @@ int dc_set_mesh(dc_ctx *c, int n, const double *pos, int t, const int *tris) {
   // Renumber the vertices on the device when the caller's numbering couples far-apart indices (typical of
   // modelling-tool exports): the packet-ELL matrix (|i - j| <= 511 over two rings) and the element windows need
   // locality. DC_RENUMBER=0 / 1 forces it off / on (development switch).
-  const char *env = getenv("DC_RENUMBER");
-  const bool want = env ? env[0] == '1' : 2 * mesh_bandwidth(t, tris) > 511;
+  const bool env = env_set("DC_RENUMBER");
+  const bool want = env_on("DC_RENUMBER", 2 * mesh_bandwidth(t, tris) > 511);
   if (want) {
     std::vector<int> order = rcm_order(n, t, tris);
     std::vector<int> inv(n);
@@ -682,12 +743,12 @@ int dc_build(dc_ctx *c) {
   if (!H.build_numerics(p.time_step, p.density, p.k_stretch, p.k_bend, p.k_att)) return fail(c, DC_ERR_TOPOLOGY, H.error);
   // every table and every kernel-set decision comes from the host-side plan (dc_tables.h); the development switches that gate tables are read here
   TableSwitches sw;
-  { const char *envw = getenv("DC_WINDOWS"); sw.windows = !(envw && envw[0] == '0'); }        // 0 keeps the global-memory corner passes
-  { const char *envd = getenv("DC_DENSE_MAX_N"); sw.dense_max_n = envd ? atoi(envd) : kDenseMaxN; }   // 0 disables, other values move the size limit
+  sw.windows = env_not_off("DC_WINDOWS", true);               // 0 keeps the global-memory corner passes
+  sw.dense_max_n = env_int("DC_DENSE_MAX_N", kDenseMaxN);     // 0 disables, other values move the size limit
                                                     // (default 2.4 MB: the matrix must stay in every XCD's 4 MB L2 next to the other tables)
-  { const char *envs = getenv("DC_SELF_LDS"); sw.self_lds = !(envs && envs[0] == '0'); }      // 0 = global-memory layer passes
-  static const char *envc = getenv("DC_ADJ_COARSE");      // 0 = block preconditioner only in the adjoint's fall-back
-  sw.adj_coarse = !(envc && atoi(envc) == 0);
+  sw.self_lds = env_not_off("DC_SELF_LDS", true);             // 0 = global-memory layer passes
+  static const bool adj_coarse = env_int("DC_ADJ_COARSE", 1) != 0;      // 0 = block preconditioner only in the adjoint's fall-back
+  sw.adj_coarse = adj_coarse;
   HostTables plan;
   plan.build(H, p, sw);
   HostDeflation *HD = nullptr;
@@ -997,9 +1058,9 @@ int dc_set_vertex_force_field(dc_ctx *c, const double *f) {
   if (!c || c->B <= 0) return fail(c, DC_ERR_STATE, "dc_set_vertex_force_field: no batch");
   if (!f) { c->fv2_set = false; return DC_OK; }
   HIPCHK(c, hipSetDevice(c->device));
-  int rc = h2d_planar(c, f, c->fv2, c->host.N, 0, true);
+  int rc = h2d_planar(c, f, c->fv2, c->host.N, true);
   if (rc) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if ((rc = stage_sync(c))) return rc;
   c->fv2_set = true;
   return DC_OK;
 }
@@ -1008,9 +1069,9 @@ int dc_set_vertex_forces(dc_ctx *c, const double *f) {
   if (!c || c->B <= 0) return fail(c, DC_ERR_STATE, "dc_set_vertex_forces: no batch");
   if (!f) { c->fv_set = false; return DC_OK; }
   HIPCHK(c, hipSetDevice(c->device));
-  int rc = h2d_planar(c, f, c->fv, c->host.N, 0, true);
+  int rc = h2d_planar(c, f, c->fv, c->host.N, true);
   if (rc) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if ((rc = stage_sync(c))) return rc;
   c->fv_set = true;
   return DC_OK;
 }
@@ -1020,8 +1081,8 @@ int dc_get_force_gradient(dc_ctx *c, double *dL_df) {
   if (rc) return rc;
   if (!dL_df) return fail(c, DC_ERR_INVALID, "dc_get_force_gradient: null output");
   // the adjoint kernel leaves y = (I + dr_df)^T u* of its last step in the work vector it shares with the forward kernel
-  if ((rc = d2h_planar(c, c->W.vbest, dL_df, c->host.N, 0, true))) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if ((rc = d2h_planar(c, c->W.vbest, dL_df, c->host.N, true))) return rc;
+  if ((rc = stage_sync(c))) return rc;
   const double h2 = c->params.time_step * c->params.time_step;
   const size_t n = (size_t) c->B * 3 * c->host.N;
   for (size_t k = 0; k < n; k++) dL_df[k] *= h2;
@@ -1045,11 +1106,9 @@ int dc_get_force_gradients(dc_ctx *c, int slot0, int nslots, double *dL_df) {
   HIPCHK(c, hipSetDevice(c->device));
   const size_t se = slot_elems(c);
   const double h2 = c->params.time_step * c->params.time_step;
-  for (int k = 0; k < nslots; k++) {
-    if ((rc = d2h_planar(c, c->YS + se * (slot0 + k), dL_df + se * k, c->host.N, k & 3, true))) return rc;
-    if ((k & 3) == 3) HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int k = 0; k < nslots; k++)
+    if ((rc = d2h_planar(c, c->YS + se * (slot0 + k), dL_df + se * k, c->host.N, true))) return rc;
+  if ((rc = stage_sync(c))) return rc;
   for (size_t q = 0; q < se * (size_t) nslots; q++) dL_df[q] *= h2;
   return cluster_check(c);
 }
@@ -1061,10 +1120,9 @@ int dc_set_state(dc_ctx *c, int slot, const double *x, const double *v) {
   HIPCHK(c, hipSetDevice(c->device));
   if (slot == c->inj_slot || slot + 1 == c->inj_slot) c->inj_slot = -1;      // a record handed in with dc_set_record described the state overwritten here
   const size_t se = slot_elems(c);
-  if ((rc = h2d_planar(c, x, c->X + se * slot, c->host.N, 0, true))) return rc;
-  if ((rc = h2d_planar(c, v, c->V + se * slot, c->host.N, 1, true))) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));   // host buffers may be reused by the caller
-  return DC_OK;
+  if ((rc = h2d_planar(c, x, c->X + se * slot, c->host.N, true))) return rc;
+  if ((rc = h2d_planar(c, v, c->V + se * slot, c->host.N, true))) return rc;
+  return stage_sync(c);   // host buffers may be reused by the caller
 }
 
 int dc_get_state(dc_ctx *c, int slot, double *x, double *v) {
@@ -1072,9 +1130,9 @@ int dc_get_state(dc_ctx *c, int slot, double *x, double *v) {
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   const size_t se = slot_elems(c);
-  if (x && (rc = d2h_planar(c, c->X + se * slot, x, c->host.N, 0, true))) return rc;
-  if (v && (rc = d2h_planar(c, c->V + se * slot, v, c->host.N, 1, true))) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (x && (rc = d2h_planar(c, c->X + se * slot, x, c->host.N, true))) return rc;
+  if (v && (rc = d2h_planar(c, c->V + se * slot, v, c->host.N, true))) return rc;
+  if ((rc = stage_sync(c))) return rc;
   return cluster_check(c);          // a state written by split kernels whose exchange timed out is not a state
 }
 
@@ -1084,17 +1142,17 @@ int dc_step_forward(dc_ctx *c, int slot, const double *fixed_pts, dc_step_stats 
   HIPCHK(c, hipSetDevice(c->device));
   const int Af = c->S.Af;
   if (fixed_pts && Af > 0) {
-    if ((rc = h2d_planar(c, fixed_pts, c->xf_cur, Af, 2, false))) return rc;
+    if ((rc = h2d_planar(c, fixed_pts, c->xf_cur, Af, false))) return rc;
     c->sched_xf[slot + 1] = 0;               // explicit targets win over a schedule entry of this step
   }
   if ((rc = enqueue_forward_steps(c, slot, 1, false, nullptr))) return rc;
   if (stats) {
     HIPCHK(c, hipMemcpyAsync(stats, c->fstats + (size_t) c->B * (slot + 1), sizeof(dc_step_stats) * c->B, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = stage_sync(c))) return rc;
     if ((rc = cluster_check(c))) return rc;
     if ((rc = check_self_overflow(c, stats, slot + 1))) return rc;
   } else if (fixed_pts && Af > 0) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = stage_sync(c))) return rc;
   }
   return DC_OK;
 }
@@ -1103,10 +1161,11 @@ int dc_get_record(dc_ctx *c, int slot, double *f, double *r) {
   int rc = check_batch(c, slot, slot);
   if (rc) return rc;
   if (slot < 1) return fail(c, DC_ERR_INVALID, "dc_get_record: slot 0 has no record");
+  HIPCHK(c, hipSetDevice(c->device));
   const size_t se = slot_elems(c);
-  if (f && (rc = d2h_planar(c, c->F + se * slot, f, c->host.N, 0, true))) return rc;
-  if (r && (rc = d2h_planar(c, c->R + se * slot, r, c->host.N, 1, true))) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (f && (rc = d2h_planar(c, c->F + se * slot, f, c->host.N, true))) return rc;
+  if (r && (rc = d2h_planar(c, c->R + se * slot, r, c->host.N, true))) return rc;
+  if ((rc = stage_sync(c))) return rc;
   return cluster_check(c);
 }
 
@@ -1114,9 +1173,10 @@ int dc_get_contacts(dc_ctx *c, int slot, int *prim_group, double *normal) {
   int rc = check_batch(c, slot, slot);
   if (rc) return rc;
   if (slot < 1) return fail(c, DC_ERR_INVALID, "dc_get_contacts: slot 0 has no record");
+  HIPCHK(c, hipSetDevice(c->device));
   const size_t se = slot_elems(c), sp = (size_t) c->B * c->host.N;
-  if (normal && (rc = d2h_planar(c, c->NRM + se * slot, normal, c->host.N, 0, true))) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (normal && (rc = d2h_planar(c, c->NRM + se * slot, normal, c->host.N, true))) return rc;
+  if ((rc = stage_sync(c))) return rc;
   if (prim_group) {
     std::vector<int> dev(sp);
     HIPCHK(c, hipMemcpy(dev.data(), c->PRIM + sp * slot, sp * sizeof(int), hipMemcpyDeviceToHost));
@@ -1166,7 +1226,7 @@ int dc_set_record(dc_ctx *c, int slot, const dc_record *rec) {
   if (!rec || !rec->x || !rec->v || !rec->f || !rec->prim || !rec->normal) return fail(c, DC_ERR_INVALID, "dc_set_record: x, v, f, prim and normal are required");
   if (rec->self_count && (!rec->self_pairs || !rec->self_layer || !rec->self_normal || !rec->self_d)) return fail(c, DC_ERR_INVALID, "dc_set_record: incomplete self-contact lists");
   HIPCHK(c, hipSetDevice(c->device));
-  const int N = c->host.N, B = c->B, Af = c->S.Af, cap = c->self_cap, np = (int) c->prims.size();
+  const int N = c->host.N, B = c->B, Af = c->S.Af, cap = c->self_cap;
   const size_t se = slot_elems(c), sp = (size_t) B * N;
   if (!c->INJ_X) {
     if ((rc = dev_alloc(c, c->batch_allocs, &c->INJ_X, se))) return rc;
@@ -1176,84 +1236,34 @@ int dc_set_record(dc_ctx *c, int slot, const dc_record *rec) {
     if ((rc = dev_alloc(c, c->batch_allocs, &c->INJ_SD, (size_t) B * cap * 3))) return rc;
   }
   c->inj_slot = -1;
+  HostRecord H;      // primitive indices and self contacts in the record layout of the kernels (dc_record.h)
+  if (!H.build(*rec, B, N, cap, (int) c->prims.size(), c->user_of, c->dev_of)) return fail(c, H.code, H.error);
   // per-vertex part: fp32 tape entries + fp64 planes (device numbering)
   struct { const double *src; float *dst32; double *dst64; } planes[5] = {
       {rec->x, c->X + se * slot, c->INJ_X}, {rec->v, c->V + se * slot, nullptr}, {rec->f, c->F + se * slot, c->INJ_F},
       {rec->r, c->R + se * slot, nullptr}, {rec->normal, c->NRM + se * slot, c->INJ_N}};
   for (auto &pl : planes) {
     if (!pl.src) continue;
-    HIPCHK(c, hipMemcpyAsync(c->stage[0], pl.src, se * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    launch_f64i_to_f32p(c->stage[0], pl.dst32, B, N, c->d_user_of, c->stream);
-    if (pl.dst64) launch_f64i_to_f64p(c->stage[0], pl.dst64, B, N, c->d_user_of, c->stream);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    double *stage;
+    if ((rc = stage_take(c, &stage))) return rc;
+    HIPCHK(c, hipMemcpyAsync(stage, pl.src, se * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    launch_f64i_to_f32p(stage, pl.dst32, B, N, c->d_user_of, c->stream);
+    if (pl.dst64) launch_f64i_to_f64p(stage, pl.dst64, B, N, c->d_user_of, c->stream);
   }
-  {
-    std::vector<int> prim(sp);
-    for (int b = 0; b < B; b++)
-      for (int i = 0; i < N; i++) {
-        const int q = rec->prim[(size_t) b * N + (c->user_of.empty() ? i : c->user_of[i])];
-        if (q >= np) return fail(c, DC_ERR_INVALID, "dc_set_record: primitive index out of range");
-        prim[(size_t) b * N + i] = q < 0 ? -1 : q;
-      }
-    HIPCHK(c, hipMemcpy(c->PRIM + sp * slot, prim.data(), sp * sizeof(int), hipMemcpyHostToDevice));
-  }
+  if ((rc = stage_sync(c))) return rc;
+  HIPCHK(c, hipMemcpy(c->PRIM + sp * slot, H.prim.data(), sp * sizeof(int), hipMemcpyHostToDevice));
   if (rec->x_fixed && Af > 0) {
-    if ((rc = h2d_planar(c, rec->x_fixed, xf_slot(c, slot), Af, 2, false))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = h2d_planar(c, rec->x_fixed, xf_slot(c, slot), Af, false))) return rc;
+    if ((rc = stage_sync(c))) return rc;
   }
-  {  // self contacts: the record layout the detection kernel leaves (dc_selflib.h): contacts by layer, pairs in device numbering (.x = the
-     // caller's smaller id), working-set slots = rank of the caller's ids among the contact vertices, offsets and counts in the meta block
-    std::vector<int> meta((size_t) B * kMetaStride, 0), verts((size_t) B * 2 * cap, 0);
-    std::vector<int2> pair((size_t) B * cap, make_int2(0, 0));
-    std::vector<float4> nrm((size_t) B * cap, make_float4(0, 0, 0, 0)), dv((size_t) B * cap, make_float4(0, 0, 0, 0));
-    std::vector<double> sn((size_t) B * cap * 3, 0.0), sd((size_t) B * cap * 3, 0.0);
-    size_t at = 0;
-    for (int b = 0; b < B && rec->self_count; b++) {
-      const int C = rec->self_count[b];
-      if (C < 0 || C > cap) return fail(c, DC_ERR_CAPACITY, "dc_set_record: more self contacts than max_self_contacts = " + std::to_string(cap));
-      int *m = meta.data() + (size_t) b * kMetaStride;
-      std::vector<int> ids, in_layer((size_t) N, -1);      // (in_layer: the last layer a vertex appeared in)
-      int nl = 0;
-      for (int k = 0; k < C; k++) {
-        const int p1 = rec->self_pairs[2 * (at + k)], p2 = rec->self_pairs[2 * (at + k) + 1], l = rec->self_layer[at + k];
-        if (p1 < 0 || p2 >= N || p1 >= p2) return fail(c, DC_ERR_INVALID, "dc_set_record: self contact pair must satisfy 0 <= id1 < id2 < N");
-        if (l < 0 || l >= kMaxLayers || (k > 0 && l < rec->self_layer[at + k - 1])) return fail(c, DC_ERR_INVALID, "dc_set_record: self contacts must come in layer order");
-        // the contacts of a layer are applied in parallel (Simulation::contactSorting, Simulation.cpp:422-624, builds them vertex-disjoint)
-        if (in_layer[p1] == l || in_layer[p2] == l) return fail(c, DC_ERR_INVALID, "dc_set_record: rollout " + std::to_string(b) + ": a vertex appears twice in self-contact layer " + std::to_string(l));
-        in_layer[p1] = in_layer[p2] = l;
-        nl = std::max(nl, l + 1);
-        ids.push_back(p1); ids.push_back(p2);
-      }
-      std::sort(ids.begin(), ids.end());
-      ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-      const int M = (int) ids.size();
-      m[0] = C; m[1] = C > 0 ? nl : 0;
-      for (int k = 0; k < C; k++) m[2 + rec->self_layer[at + k] + 1]++;
-      for (int l = 0; l < nl; l++) m[2 + l + 1] += m[2 + l];
-      m[kMetaStride - 1] = M; m[kMetaStride - 2] = 0; m[kMetaStride - 3] = C;
-      for (int q = 0; q < M; q++) verts[(size_t) b * 2 * cap + q] = c->dev_of.empty() ? ids[q] : c->dev_of[ids[q]];
-      for (int k = 0; k < C; k++) {
-        const int p1 = rec->self_pairs[2 * (at + k)], p2 = rec->self_pairs[2 * (at + k) + 1];
-        const int s1 = (int) (std::lower_bound(ids.begin(), ids.end(), p1) - ids.begin()), s2 = (int) (std::lower_bound(ids.begin(), ids.end(), p2) - ids.begin());
-        const size_t o = (size_t) b * cap + k;
-        pair[o] = make_int2(c->dev_of.empty() ? p1 : c->dev_of[p1], c->dev_of.empty() ? p2 : c->dev_of[p2]);
-        const int slots = s1 | (s2 << 16);
-        float w; std::memcpy(&w, &slots, sizeof(float));
-        nrm[o] = make_float4((float) rec->self_normal[3 * (at + k)], (float) rec->self_normal[3 * (at + k) + 1], (float) rec->self_normal[3 * (at + k) + 2], w);
-        dv[o] = make_float4((float) rec->self_d[3 * (at + k)], (float) rec->self_d[3 * (at + k) + 1], (float) rec->self_d[3 * (at + k) + 2], 0.f);
-        for (int d = 0; d < 3; d++) { sn[3 * o + d] = rec->self_normal[3 * (at + k) + d]; sd[3 * o + d] = rec->self_d[3 * (at + k) + d]; }
-      }
-      at += C;
-    }
-    const SelfRec R = self_slot(c, slot);
-    HIPCHK(c, hipMemcpy(R.meta, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(R.pair, pair.data(), pair.size() * sizeof(int2), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(R.nrm, nrm.data(), nrm.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(R.dvec, dv.data(), dv.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(R.verts, verts.data(), verts.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->INJ_SN, sn.data(), sn.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->INJ_SD, sd.data(), sd.size() * sizeof(double), hipMemcpyHostToDevice));
-  }
+  const SelfRec R = self_slot(c, slot);
+  HIPCHK(c, hipMemcpy(R.meta, H.meta.data(), H.meta.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(R.pair, H.pair.data(), H.pair.size() * sizeof(int2), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(R.nrm, H.nrm.data(), H.nrm.size() * sizeof(float4), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(R.dvec, H.dvec.data(), H.dvec.size() * sizeof(float4), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(R.verts, H.verts.data(), H.verts.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->INJ_SN, H.sn.data(), H.sn.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->INJ_SD, H.sd.data(), H.sd.size() * sizeof(double), hipMemcpyHostToDevice));
   c->inj_slot = slot;
   return DC_OK;
 }
@@ -1267,27 +1277,22 @@ int dc_step_backward(dc_ctx *c, int slot, const double *dL_dxnew, const double *
   if (!dL_dxnew || !dL_dvnew || !dL_dx || !dL_dv) return fail(c, DC_ERR_INVALID, "dc_step_backward: null gradient");
   HIPCHK(c, hipSetDevice(c->device));
   const int N = c->host.N, Af = c->S.Af, G = c->S.ngroups;
-  if ((rc = h2d_planar(c, dL_dxnew, c->GX, N, 0, true))) return rc;
-  if ((rc = h2d_planar(c, dL_dvnew, c->GV, N, 1, true))) return rc;
-  const bool with_init = dL_dxinit && dL_dvinit;
+  if ((rc = h2d_planar(c, dL_dxnew, c->GX, N, true))) return rc;
+  if ((rc = h2d_planar(c, dL_dvnew, c->GV, N, true))) return rc;
+  const bool with_init = dL_dxinit && dL_dvinit, start = is_start != 0;
   if (with_init) {
-    if ((rc = h2d_planar(c, dL_dxinit, c->IX, N, 2, true))) return rc;
-    if ((rc = h2d_planar(c, dL_dvinit, c->IV, N, 3, true))) return rc;
+    if ((rc = h2d_planar(c, dL_dxinit, c->IX, N, true))) return rc;
+    if ((rc = h2d_planar(c, dL_dvinit, c->IV, N, true))) return rc;
   }
   HIPCHK(c, hipMemsetAsync(c->DMU, 0, sizeof(float) * c->B * G, c->stream));
-  if (Af > 0) HIPCHK(c, hipMemsetAsync(dxf_slot(c, slot), 0, sizeof(float) * xf_elems(c), c->stream));
-  {
-    BwdArgs BA = bwd_args(c, slot, is_start != 0, with_init);
-    if (!with_init) { BA.ix = nullptr; BA.iv = nullptr; BA.slot_ix = 0; }     // the per-step call takes its seeds from its arguments only
-    if ((rc = enqueue_adjoint_step(c, BA))) return rc;
-  }
-  if ((rc = d2h_planar(c, c->GX, dL_dx, N, 0, true))) return rc;
-  if ((rc = d2h_planar(c, c->GV, dL_dv, N, 1, true))) return rc;
-  if (dL_dxfixed && Af > 0 && (rc = d2h_planar(c, dxf_slot(c, slot), dL_dxfixed, Af, 2, false))) return rc;
+  if ((rc = enqueue_backward_steps(c, slot, 1, with_init ? Seeds::init : Seeds::none, &start, nullptr))) return rc;
+  if ((rc = d2h_planar(c, c->GX, dL_dx, N, true))) return rc;
+  if ((rc = d2h_planar(c, c->GV, dL_dv, N, true))) return rc;
+  if (dL_dxfixed && Af > 0 && (rc = d2h_planar(c, dxf_slot(c, slot), dL_dxfixed, Af, false))) return rc;
   std::vector<float> dmu((size_t) c->B * G);
   HIPCHK(c, hipMemcpyAsync(dmu.data(), c->DMU, dmu.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   if (stats) HIPCHK(c, hipMemcpyAsync(stats, c->bstats + (size_t) c->B * slot, sizeof(dc_bwd_stats) * c->B, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if ((rc = stage_sync(c))) return rc;
   if ((rc = cluster_check(c))) return rc;
   if (dL_dmu) for (size_t k = 0; k < dmu.size(); k++) dL_dmu[k] = dmu[k];
   return DC_OK;
@@ -1351,18 +1356,13 @@ int dc_step_backward_dev(dc_ctx *c, int slot, const void *d_dL_dxnew, const void
   const int N = c->host.N, Af = c->S.Af, G = c->S.ngroups;
   launch_dev_to_planar(d_dL_dxnew, is_f32, c->GX, c->B, N, c->d_user_of, c->stream);
   launch_dev_to_planar(d_dL_dvnew, is_f32, c->GV, c->B, N, c->d_user_of, c->stream);
-  const bool with_init = d_dL_dxinit && d_dL_dvinit;
+  const bool with_init = d_dL_dxinit && d_dL_dvinit, start = is_start != 0;
   if (with_init) {
     launch_dev_to_planar(d_dL_dxinit, is_f32, c->IX, c->B, N, c->d_user_of, c->stream);
     launch_dev_to_planar(d_dL_dvinit, is_f32, c->IV, c->B, N, c->d_user_of, c->stream);
   }
   HIPCHK(c, hipMemsetAsync(c->DMU, 0, sizeof(float) * c->B * G, c->stream));
-  if (Af > 0) HIPCHK(c, hipMemsetAsync(dxf_slot(c, slot), 0, sizeof(float) * xf_elems(c), c->stream));
-  {
-    BwdArgs BA = bwd_args(c, slot, is_start != 0, with_init);
-    if (!with_init) { BA.ix = nullptr; BA.iv = nullptr; BA.slot_ix = 0; }
-    if ((rc = enqueue_adjoint_step(c, BA))) return rc;
-  }
+  if ((rc = enqueue_backward_steps(c, slot, 1, with_init ? Seeds::init : Seeds::none, &start, nullptr))) return rc;
   launch_planar_to_dev(c->GX, d_dL_dx, is_f32, c->B, N, c->d_user_of, c->stream);
   launch_planar_to_dev(c->GV, d_dL_dv, is_f32, c->B, N, c->d_user_of, c->stream);
   if (d_dL_dxfixed && Af > 0) launch_planar_to_dev(dxf_slot(c, slot), d_dL_dxfixed, is_f32, c->B, Af, nullptr, c->stream);
@@ -1401,25 +1401,9 @@ int dc_rollout_backward(dc_ctx *c, int slot, int nsteps) {
   if (rc) return rc;
   if (slot - nsteps + 1 < 1) return fail(c, DC_ERR_INVALID, "dc_rollout_backward: would run past slot 1");
   if ((rc = kernel_time_begin(c))) return rc;
-  if (c->SEEDX) {
-    int ns = 0;
-    for (int k = 0; k < nsteps; k++) ns += c->sched_seed[slot - k - 1];
-    if (ns % nsteps) return fail(c, DC_ERR_INVALID, "dc_rollout_backward: the seed schedule covers only part of the slots " + std::to_string(slot - nsteps) + " .. " + std::to_string(slot - 1));
-  }
-  if (c->S.Af > 0) HIPCHK(c, hipMemsetAsync(dxf_slot(c, slot - nsteps + 1), 0, sizeof(float) * xf_elems(c) * nsteps, c->stream));
-  const bool inj_inside = c->inj_slot >= slot - nsteps + 1 && c->inj_slot <= slot;      // (dc_set_record: that step gets a launch of its own)
-  const bool fused_bwd = fuse_steps_enabled() && nsteps > 1 && !inj_inside && c->params.adjoint_mode != 2;     // (mode 2: assemble -> factor -> step per step)
-  if (fused_bwd) {
-    BwdArgs A = bwd_args(c, slot, slot == c->start_slot + 1, false);
-    A.nsteps = nsteps;                       // the whole sweep of a rollout in one launch
-    if ((rc = enqueue_adjoint_step(c, A))) return rc;
-  } else {
-    for (int k = 0; k < nsteps; k++) {
-      const int s = slot - k;
-      if ((rc = enqueue_adjoint_step(c, bwd_args(c, s, s == c->start_slot + 1, false)))) return rc;   // isStart: Simulation.cpp:3947
-    }
-  }
-  return kernel_time_end(c, true, fused_bwd ? 1 : nsteps);
+  int launches = 0;
+  if ((rc = enqueue_backward_steps(c, slot, nsteps, Seeds::schedule, nullptr, &launches))) return rc;
+  return kernel_time_end(c, true, launches);
 }
 
 int dc_set_trajectory_start(dc_ctx *c, int start_slot) {
@@ -1432,10 +1416,11 @@ int dc_set_trajectory_start(dc_ctx *c, int start_slot) {
 int dc_get_gradient(dc_ctx *c, double *dL_dx, double *dL_dv, double *dL_dmu) {
   int rc = check_batch(c, 0, 0);
   if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
   const int N = c->host.N, G = c->S.ngroups;
-  if (dL_dx && (rc = d2h_planar(c, c->GX, dL_dx, N, 0, true))) return rc;
-  if (dL_dv && (rc = d2h_planar(c, c->GV, dL_dv, N, 1, true))) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (dL_dx && (rc = d2h_planar(c, c->GX, dL_dx, N, true))) return rc;
+  if (dL_dv && (rc = d2h_planar(c, c->GV, dL_dv, N, true))) return rc;
+  if ((rc = stage_sync(c))) return rc;
   if (dL_dmu) {
     std::vector<float> dmu((size_t) c->B * G);
     HIPCHK(c, hipMemcpy(dmu.data(), c->DMU, dmu.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -1455,12 +1440,10 @@ int dc_set_fixed_point_schedule(dc_ctx *c, int slot0, int nsteps, const double *
   HIPCHK(c, hipSetDevice(c->device));
   const size_t per = xf_elems(c);
   for (int k = 0; k < nsteps; k++) {
-    if ((rc = h2d_planar(c, xf + per * k, xf_slot(c, slot0 + k + 1), Af, k & 3, false))) return rc;
+    if ((rc = h2d_planar(c, xf + per * k, xf_slot(c, slot0 + k + 1), Af, false))) return rc;
     c->sched_xf[slot0 + k + 1] = 1;
-    if ((k & 3) == 3) HIPCHK(c, hipStreamSynchronize(c->stream));      // the four staging buffers are reused
   }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return DC_OK;
+  return stage_sync(c);
 }
 
 int dc_set_force_schedule(dc_ctx *c, int slot0, int nsteps, const double *fu, const double *fv_scale) {
@@ -1495,13 +1478,12 @@ int dc_set_seed_schedule(dc_ctx *c, int slot0, int nslots, const double *dL_dx, 
   }
   const int N = c->host.N;
   for (int k = 0; k < nslots; k++) {
-    if ((rc = h2d_planar(c, dL_dx + (size_t) 3 * N * c->B * k, seedx_slot(c, slot0 + k), N, 0, true))) return rc;
-    if (dL_dv) { if ((rc = h2d_planar(c, dL_dv + (size_t) 3 * N * c->B * k, seedv_slot(c, slot0 + k), N, 1, true))) return rc; }
+    if ((rc = h2d_planar(c, dL_dx + se * k, seedx_slot(c, slot0 + k), N, true))) return rc;
+    if (dL_dv) { if ((rc = h2d_planar(c, dL_dv + se * k, seedv_slot(c, slot0 + k), N, true))) return rc; }
     else HIPCHK(c, hipMemsetAsync(seedv_slot(c, slot0 + k), 0, se * sizeof(float), c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
     c->sched_seed[slot0 + k] = 1;
   }
-  return DC_OK;
+  return stage_sync(c);
 }
 
 int dc_clear_schedules(dc_ctx *c) {
@@ -1516,11 +1498,10 @@ int dc_set_gradient(dc_ctx *c, const double *dL_dx, const double *dL_dv) {
   if (rc) return rc;
   if (!dL_dx || !dL_dv) return fail(c, DC_ERR_INVALID, "dc_set_gradient: null gradient");
   HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = h2d_planar(c, dL_dx, c->GX, c->host.N, 0, true))) return rc;
-  if ((rc = h2d_planar(c, dL_dv, c->GV, c->host.N, 1, true))) return rc;
+  if ((rc = h2d_planar(c, dL_dx, c->GX, c->host.N, true))) return rc;
+  if ((rc = h2d_planar(c, dL_dv, c->GV, c->host.N, true))) return rc;
   HIPCHK(c, hipMemsetAsync(c->DMU, 0, sizeof(float) * c->B * c->S.ngroups, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return DC_OK;
+  return stage_sync(c);
 }
 
 int dc_get_states(dc_ctx *c, int slot0, int nslots, double *x, double *v) {
@@ -1530,11 +1511,10 @@ int dc_get_states(dc_ctx *c, int slot0, int nslots, double *x, double *v) {
   HIPCHK(c, hipSetDevice(c->device));
   const size_t se = slot_elems(c);
   for (int k = 0; k < nslots; k++) {
-    if (x && (rc = d2h_planar(c, c->X + se * (slot0 + k), x + se * k, c->host.N, 0, true))) return rc;
-    if (v && (rc = d2h_planar(c, c->V + se * (slot0 + k), v + se * k, c->host.N, 1, true))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (x && (rc = d2h_planar(c, c->X + se * (slot0 + k), x + se * k, c->host.N, true))) return rc;
+    if (v && (rc = d2h_planar(c, c->V + se * (slot0 + k), v + se * k, c->host.N, true))) return rc;
   }
-  return DC_OK;
+  return stage_sync(c);
 }
 
 int dc_get_dxfixed(dc_ctx *c, int slot0, int nslots, double *dL_dxfixed) {
@@ -1545,17 +1525,16 @@ int dc_get_dxfixed(dc_ctx *c, int slot0, int nslots, double *dL_dxfixed) {
   if (Af <= 0) return DC_OK;
   HIPCHK(c, hipSetDevice(c->device));
   const size_t per = xf_elems(c);
-  for (int k = 0; k < nslots; k++) {
-    if ((rc = d2h_planar(c, dxf_slot(c, slot0 + k), dL_dxfixed + per * k, Af, 2, false))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return DC_OK;
+  for (int k = 0; k < nslots; k++)
+    if ((rc = d2h_planar(c, dxf_slot(c, slot0 + k), dL_dxfixed + per * k, Af, false))) return rc;
+  return stage_sync(c);
 }
 
 int dc_get_param_gradients(dc_ctx *c, int slot, double *out) {
   int rc = check_batch(c, slot, slot);
   if (rc) return rc;
   if (slot < 1 || !out) return fail(c, DC_ERR_INVALID, "dc_get_param_gradients: slot 0 has no record");
+  HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   std::vector<float> v((size_t) c->B * 8);
   HIPCHK(c, hipMemcpy(v.data(), dpar_slot(c, slot), v.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -1634,7 +1613,7 @@ int dc_get_adjoint_matrix(dc_ctx *c, int slot, int rollout, double *K) {
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = dense_ensure(c))) return rc;
   const DenseAdjWork &D = c->dense;
-  launch_dense_assemble(c->S, bwd_args(c, slot, false, false), c->W.x64, D, rollout, 1, c->stream);
+  launch_dense_assemble(c->S, bwd_args(c, slot, false, Seeds::none), c->W.x64, D, rollout, 1, c->stream);
   HIPCHK(c, hipGetLastError());
   std::vector<double> Kd((size_t) D.ld * n);
   HIPCHK(c, hipMemcpyAsync(Kd.data(), D.K, Kd.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));

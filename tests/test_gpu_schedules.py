@@ -255,3 +255,92 @@ def test_several_attachment_sets_in_fused_batched_rollouts_by_composing_contexts
     e_fa, e_fb = rel(a["dxfA"], b["dxfA"]), rel(a["dxfB"], b["dxfB"])
     print(f"\n[attachment sets, fused segments vs per-step calls] dL_dx {e_dx:.2e} dL_dv {e_dv:.2e} dL_dxfixed set A {e_fa:.2e} set B {e_fb:.2e}")
     assert max(e_dx, e_dv, e_fa, e_fb) <= 1e-5 and np.linalg.norm(a["dxfA"]) > 0 and np.linalg.norm(a["dxfB"]) > 0
+
+
+def test_the_four_ways_through_a_backward_sweep_agree():
+    """One fused dc_rollout_backward(3), three dc_rollout_backward(1), three dc_step_backward chained through the host and three
+    dc_step_backward_dev chained on the device in fp64 tensors all enqueue the same adjoint steps (enqueue_backward_steps, dc_engine.hip) on an
+    8 x 8 cloth with two clips on the sphere (sliding contacts), B = 2, gradient clipping at its default: dL_dx, dL_dv and dL_dxfixed of every slot agree
+    BITWISE (fused = stepwise; fp32 values survive the round trip through the host's fp64 exactly). dL_dmu is an fp32
+    running sum in the rollout calls and one fp32 term per call in the per-step ones: |sum of the terms - sum| <= 4 * 2^-24 * sum |terms|, the
+    fp32 bound for three additions. The per-step calls take their seeds from their arguments only: a seed schedule on their slots changes
+    nothing for them, and does for the rollout call."""
+    nx, B, S = 8, 2, 3
+    V, F = meshes.grid_cloth(nx, nx, 4.5, 4.5, "DOWN")
+    V = f32(V)
+    N, att = V.shape[0], (0, nx - 1)
+    e = capi.Engine(0)
+    e.set_mesh(V, F)
+    e.set_attachments(att)
+    e.set_params(time_step=1 / 180, density=0.3, k_stretch=150.0, k_bend=0.05, forward_tol=1e-7, backward_tol=1e-7, cg_rel_tol=1e-5,
+                 cg_max_iter=2000, selfcollision_enabled=0, adjoint_mode=1, adjoint_rel_tol=1e-7)
+    assert e.params.gradient_clipping == 1 and e.params.gradient_clipping_threshold == 16.0
+    e.set_primitives([dict(kind=capi.DC_PRIM_SPHERE, group=0, center=f32(meshes.sphere_scene_center(V, 2.0)), radius=2.0, mu=0.05)])
+    e.build()
+    e.alloc_batch(B, S)
+    # pressed onto the sphere and moving across it: contacts that slide (dL_dmu comes from the sliding ones)
+    X0 = np.stack([f32(V.reshape(-1) + np.tile([0.01 * b, -0.06, 0.0], N)) for b in range(B)])
+    e.set_state(0, X0, np.stack([f32(np.tile([1.0 + 0.25 * b, 0.0, 0.5], N)) for b in range(B)]))
+    e.rollout_forward(0, S)
+    assert all(np.all(e.get_stats(s)[0]["prim_contacts"] > 0) for s in range(1, S + 1))
+    rng = np.random.default_rng(3)
+    gx = f32(rng.standard_normal(X0.shape)); gv = f32(0.01 * rng.standard_normal(X0.shape))
+    seeds = f32(1e-1 * rng.standard_normal((S, B, 3 * N)))          # loss gradient w.r.t. the states of slots 0 .. S - 1
+    zero = np.zeros_like(gx)
+    dev = torch.device("cuda", 0)
+
+    def rollout(nsteps):
+        e.set_gradient(gx, gv)
+        for s in range(S, 0, -nsteps):
+            e.rollout_backward(s, nsteps)
+        dx, dv, dmu = e.get_gradient()
+        return dict(dx=dx, dv=dv, dxf=e.get_dxfixed(1, S), dmu=dmu)
+
+    def host_steps(init=None):
+        cx, cv, dxf, terms = gx, gv, [None] * S, []
+        for s in range(S, 0, -1):
+            o = e.step_backward(s, cx, cv, dL_dxinit=None if init is None else init[s - 1], dL_dvinit=None if init is None else zero, is_start=(s == 1))
+            cx, cv, dxf[s - 1] = o["dL_dx"], o["dL_dv"], o["dL_dxfixed"].copy()
+            terms.append(o["dL_dmu"].copy())
+        return dict(dx=cx, dv=cv, dxf=np.stack(dxf), terms=np.stack(terms))
+
+    def dev_steps():
+        t = lambda a: torch.tensor(np.ascontiguousarray(a).reshape(-1), dtype=torch.float64, device=dev)
+        cx, cv, dxf, terms = t(gx), t(gv), [None] * S, []
+        for s in range(S, 0, -1):
+            dx, dv = torch.empty_like(cx), torch.empty_like(cv)
+            xf = torch.empty(B * 3 * len(att), dtype=torch.float64, device=dev); mu = torch.empty(B, dtype=torch.float64, device=dev)
+            e.step_backward_dev(s, cx, cv, dx, dv, dxfixed=xf, dmu=mu, is_start=(s == 1))
+            cx, cv, dxf[s - 1] = dx, dv, xf
+            terms.append(mu)
+        torch.cuda.synchronize()
+        e.sync()
+        h = lambda a, shape: a.cpu().numpy().reshape(shape)
+        return dict(dx=h(cx, gx.shape), dv=h(cv, gx.shape), dxf=np.stack([h(a, (B, 3 * len(att))) for a in dxf]), terms=np.stack([h(a, (B, 1)) for a in terms]))
+
+    def same(a, b):
+        for key in ("dx", "dv", "dxf"):
+            np.testing.assert_array_equal(a[key], b[key], err_msg=key)
+
+    fused, single, host, devc = rollout(S), rollout(1), host_steps(), dev_steps()
+    assert np.abs(fused["dx"]).max() > 0 and np.abs(fused["dxf"]).max() > 0
+    same(fused, single); same(fused, host); same(fused, devc)
+    np.testing.assert_array_equal(host["terms"], devc["terms"])
+    total, mag = host["terms"].sum(axis=0), np.abs(host["terms"]).sum(axis=0)
+    print(f"\n[backward four ways] dL_dmu: sum of the per-step terms {total.ravel()}, fused {fused['dmu'].ravel()}, stepwise {single['dmu'].ravel()}, "
+          f"bound {(4 * 2.0 ** -24 * mag).ravel()}")
+    assert np.all(mag > 0)
+    for r in (fused, single):
+        assert np.all(np.abs(total - r["dmu"]) <= 4 * 2.0 ** -24 * mag)
+
+    # a seed schedule on the slots the steps started from: nothing for the per-step calls, seeds for the rollout call (all steps or none)
+    e.set_seed_schedule(0, seeds)
+    host_s, dev_s = host_steps(), dev_steps()
+    same(host_s, host); same(dev_s, host)
+    np.testing.assert_array_equal(host_s["terms"], host["terms"]); np.testing.assert_array_equal(dev_s["terms"], host["terms"])
+    fused_s, single_s, host_i = rollout(S), rollout(1), host_steps(init=seeds)
+    same(fused_s, single_s)
+    print(f"[backward four ways] with seeds: rollout vs per-step calls given them as init gradients: dL_dx {rel(fused_s['dx'], host_i['dx']):.2e} "
+          f"dL_dv {rel(fused_s['dv'], host_i['dv']):.2e} dL_dxfixed {rel(fused_s['dxf'], host_i['dxf']):.2e}; against no seeds: dL_dx {rel(fused_s['dx'], fused['dx']):.2e}")
+    same(fused_s, host_i)
+    assert rel(fused_s["dx"], fused["dx"]) > 1e-3

@@ -17,6 +17,19 @@ def test_packet_window_and_rcm_tables(tmp_path):
     assert r.returncode == 0 and r.stdout.strip().endswith("ALL OK"), r.stdout + r.stderr
 
 
+def test_record_import_lays_out_the_callers_self_contacts(tmp_path):
+    """csrc/dc_record.cpp, the host part of dc_set_record, on 8 vertices, max_self_contacts = 4 and two rollouts against answers written out by
+    hand (tests/native/record_import_check.cpp): layer offsets and tail of the meta block, working-set ranks bit-for-bit in nrm.w, pairs, verts
+    and primitive indices in device numbering under a renumbering, the running offset into the concatenated lists, every rejection."""
+    csrc = os.path.join(ROOT, "diffcloth_amd", "csrc")
+    exe = str(tmp_path / "record_import_check")
+    srcs = [os.path.join(ROOT, "tests", "native", "record_import_check.cpp"), os.path.join(csrc, "dc_record.cpp")]
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-I", csrc, "-o", exe] + srcs)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    print(r.stdout)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ALL OK"), r.stdout + r.stderr
+
+
 def test_deflation_builder_finds_the_lowest_eigenvectors(tmp_path):
     """csrc/dc_deflate.cpp on a synthetic badly graded strip (cells shrinking 100 x across the sheet): the Chebyshev-filtered subspace
     iteration returns orthonormal vectors whose eigen-residuals |A u - theta u| are small, (U^T A U)^-1 is consistent, in well under a
