@@ -18,6 +18,7 @@
 #define DC_KERNEL_TU
 #include <cstdlib>
 #include "dc_devlib.h"
+#include "dc_env.h"
 #include "dc_winlib.h"
 #include "dc_denselib.h"
 #include "dc_adjprecond.h"
@@ -1013,7 +1014,7 @@ __global__ __launch_bounds__(THREADS) void k_adjoint_step(const DevSystem *__res
 }
 
 static int pick_threads_bwd(int N) {
-  static const int forced = getenv("DC_BWD_THREADS") ? atoi(getenv("DC_BWD_THREADS")) : 0;     // development switch
+  static const int forced = env_int("DC_BWD_THREADS", 0);     // development switch
   if (forced == 256 || forced == 512 || forced == 1024) return forced;
   // 16 waves per rollout at every mesh size: the Krylov iteration is a chain of barrier-separated phases with global-memory
   // round trips, and with one workgroup per CU (256 rollouts) only the waves of that workgroup can hide them — measured

@@ -7,7 +7,9 @@
 #include <cstring>
 #include <string>
 #include <vector>
+#include "dc_clusterplan.h"
 #include "dc_context.h"
+#include "dc_env.h"
 #include "dc_record.h"
 #include "dc_tables.h"
 #include "dc_spheremesh.h"
@@ -23,16 +25,10 @@ hipError_t launch_adjoint_step_cluster(const DevSystem &S, const DevCluster &CL,
 static_assert(rec::kMetaStride == kMetaStride && rec::kMaxLayers == kMaxLayers, "dc_record.h restates dc_device.h's record sizes");
 static_assert(sizeof(rec::Int2) == sizeof(int2) && alignof(rec::Int2) == alignof(int2), "dc_record.h: Int2 is uploaded as int2");
 static_assert(sizeof(rec::Float4) == sizeof(float4) && alignof(rec::Float4) == alignof(float4), "dc_record.h: Float4 is uploaded as float4");
+static_assert(cplan::kXchWaves == kXchWaves && cplan::kXchLdsFloats == kXchLdsFloats && cplan::kSpinLimit == kSpinLimit, "dc_clusterplan.h restates dc_cluster.h's exchange sizes");
+static_assert(cplan::kSelfDetectLdsInts == kSelfDetectLdsInts && cplan::kGranuleBytes == sizeof(v4i), "dc_clusterplan.h restates dc_selftmp.h's LDS need and the granule size");
 
 namespace {
-
-// The development switches of this file, one spelling per parse rule (DESIGN.md section 1 lists every switch with its rule, default and
-// the time it is read). env_on: only a value that starts with 1 enables; env_not_off: any value that does not start with 0 enables;
-// both give dflt when the variable is not set. env_int: atoi of the value.
-bool env_set(const char *name) { return getenv(name) != nullptr; }
-bool env_on(const char *name, bool dflt) { const char *e = getenv(name); return e ? e[0] == '1' : dflt; }
-bool env_not_off(const char *name, bool dflt) { const char *e = getenv(name); return e ? e[0] != '0' : dflt; }
-int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
 
 template <typename T>
 int dev_alloc(dc_ctx *c, std::vector<void *> &pool, T **out, size_t count) {
@@ -216,112 +212,41 @@ void free_cluster(dc_ctx *c) {
   c->cl = ClusterSet();
 }
 
-template <typename T, typename U>
-int upload_cl(dc_ctx *c, const T **out, const std::vector<U> &src) {
-  std::vector<T> tmp(src.begin(), src.end());
-  T *p = nullptr;
-  int rc = dev_alloc(c, c->cl.allocs, &p, tmp.size());
-  if (rc) return rc;
-  if (!tmp.empty()) HIPCHK(c, hipMemcpy(p, tmp.data(), tmp.size() * sizeof(T), hipMemcpyHostToDevice));
-  *out = p;
-  return DC_OK;
-}
-
-// Rollouts one launch of the split kernels can hold with EVERY workgroup resident (the exchange spins on its peers: a part that is not
-// scheduled until another rollout has finished its whole sweep would let them run into the spin limit). A launch is padded to a
-// multiple of 8 rollouts and the parts of rollout j all run on XCD j mod 8 (cluster_map, dc_cluster.h), so what bounds it is one XCD:
-// ceil(nb / 8) * K workgroups on cus / 8 CUs, one workgroup (160 KB of LDS, up to 1024 threads) per CU.
-static int cluster_capacity(int cus, int K) { return std::max(1, 8 * ((cus / 8) / std::max(K, 1))); }
-
-// Tables for K parts per rollout; returns DC_OK with c->cl.ok = false when K does not fit this mesh (the caller tries K - 1).
-int build_cluster(dc_ctx *c, int K, bool forced) {
-  free_cluster(c);
-  const HostSystem &H = c->host;
-  const int N = H.N;
-  if (K < 2 || c->bandwidth <= 0 || c->bandwidth > 511) return DC_OK;
-  const int HB = std::max(64, round64(c->bandwidth));
-  static const int allowed[] = {1, 2, 3, 4, 6, 8, 12};
-  const int lds_cap = (160 * 1024 - 256) / 4 - kXchLdsFloats;      // floats
-  HostWindows HW;
-  int R = 0, wpp = 0, vpt = 0;
-  for (int w = 1; w <= 8 && R == 0; w++) {
-    const int own_w = round64((N + K * w - 1) / (K * w));
-    const int Rc = own_w * w;
-    if ((long long) (K - 1) * Rc >= N) break;           // a part would be empty
-    if (Rc < HB) break;                                  // halo rows must come from the direct neighbours only
-    if (Rc < 256 && !forced) break;                      // parts of fewer rows than half a workgroup: nothing left to save (the 1426-vertex
-                                                         // T-shirt, one rollout: 21.9 / 19.0 / 18.4 / 18.2 ms per fwd+bwd step at K = 1 / 4 / 6 / 8
-                                                         // once its parts share an XCD, tools/bench_tshirt_k.py)
-    int v = 0;
-    for (int a : allowed) if (a * 512 >= Rc) { v = a; break; }
-    if (v == 0) continue;                                // more rows per part than the kernel holds in registers: more windows do not help
-    if (!HW.build_own(H, own_w)) continue;
-    const int win_floats = (int) (HW.lds_bytes / 4);
-    const int fwd = std::max(std::max((v <= 6 ? 6 : 3) * (Rc + 2 * HB), win_floats), kSelfDetectLdsInts);      // (<= 6 rows per thread: pipelined CG, two gather arrays)
-    const int bwd = (win_floats + 3) / 4 * 4 + 6 * HB;
-    if (fwd + 4 > lds_cap || bwd + 4 > lds_cap) continue;
-    // the element reach of every window must stay inside the boundary rows its part receives
-    bool reach_ok = true;
-    for (int q = 0; q < HW.nwin; q++) {
-      const int part = q / w, p0 = part * Rc;
-      const int lo = HW.win[8 * q + 2], vs = HW.win[8 * q + 3];
-      if (lo < p0 - HB || lo + vs > p0 + Rc + HB) reach_ok = false;
-    }
-    if (!reach_ok) continue;
-    R = Rc; wpp = w; vpt = v;
-  }
-  if (R == 0) return DC_OK;
-  HostPackets HP;
-  if (!HP.build_rows(H, K * R)) return DC_OK;
+// The tables of a split plan and the exchange area of one launch, uploaded; c->cl.ok only when all of it is there (what a failed allocation
+// leaves behind stays in c->cl.allocs for free_cluster).
+int upload_cluster(dc_ctx *c, const ClusterPlan &P) {
   ClusterSet &cl = c->cl;
   DevCluster &D = cl.D;
   std::memset(&D, 0, sizeof(D));
-  D.K = K; D.R = R; D.HB = HB; D.wpp = wpp; D.xch_stride = kXchWaves + 2 * HB; D.pk_vpt = vpt;
-  D.spin_limit = kSpinLimit; D.test_drop = 0; D.test_skew = -1;
-  D.redundant_self = env_on("DC_SELF_REDUNDANT", true);
-  { const long long ms = env_int("DC_TEST_SPIN_MS", 0); if (ms > 0) D.spin_limit = ms * 100000ll; }      // test hooks
-  D.test_drop = env_on("DC_TEST_DROP_PART", false);
-  D.test_skew = env_int("DC_TEST_SKEW_PART", -1);
-  int rc;
-  const int *ip; const float *fp;
-  if ((rc = upload_cl<int>(c, &ip, HW.win))) return rc;
-  D.win = (const int4 *) ip;
-  if ((rc = upload_cl<int>(c, &ip, HW.tri_rec))) return rc;
-  D.wtri_rec = (const int4 *) ip;
-  if ((rc = upload_cl<float>(c, &fp, HW.tri_D))) return rc;
-  D.wtri_D = (const float4 *) fp;
-  if ((rc = upload_cl<int>(c, &ip, HW.bend_rec))) return rc;
-  D.wbend_rec = (const int4 *) ip;
-  if ((rc = upload_cl<float>(c, &fp, HW.bend_w))) return rc;
-  D.wbend_w = (const float4 *) fp;
-  if ((rc = upload_cl<float>(c, &fp, HW.tri_Dlo))) return rc;
-  D.wtri_Dlo = (const float4 *) fp;
-  if ((rc = upload_cl<float>(c, &fp, HW.bend_lo))) return rc;
-  D.wbend_lo = (const float4 *) fp;
-  if ((rc = upload_cl<int>(c, &ip, HW.inc))) return rc;
-  D.winc = (const int4 *) ip;
-  if ((rc = upload_cl<int>(c, &D.winc_ptr, HW.inc_ptr))) return rc;
-  if ((rc = upload_cl<int>(c, &D.winc_n, HW.inc_n))) return rc;
+  D.K = P.K; D.R = P.R; D.HB = P.HB; D.wpp = P.wpp; D.nb = P.nb; D.xch_stride = P.xch_stride; D.pk_vpt = P.pk_vpt;
+  D.spin_limit = P.spin_limit; D.redundant_self = P.redundant_self; D.test_drop = P.test_drop; D.test_skew = P.test_skew;
+  const HostWindows &HW = P.win;
+  const HostPackets &HP = P.pk;
   D.nwin = HW.nwin; D.win_vcap = HW.vcap; D.win_nrcap = HW.nrcap; D.win_lds_bytes = (int) HW.lds_bytes;
-  if ((rc = upload_cl<int>(c, &ip, HP.pk))) return rc;
-  D.pk = (const int4 *) ip;
-  if ((rc = upload_cl<int>(c, &D.pk_ptr, HP.pk_ptr))) return rc;
-  if ((rc = upload_cl<int>(c, &D.pk_n, HP.pk_n))) return rc;
-  if ((rc = upload_cl<float>(c, &D.sq_dinv, HP.sq_dinv))) return rc;
-  cl.K = K;
-  {   // rollouts per launch: all of them when they fit, else equal chunks (never a last launch with a handful of rollouts)
-    const int nbmax = cluster_capacity(c->cus, K), nchunks = (c->B + nbmax - 1) / nbmax;
-    cl.nb = std::max(1, (c->B + nchunks - 1) / nchunks);
+  // (host vector, the DevCluster pointer it goes behind): int and float tables alike are flat arrays of 4-byte elements
+  const struct { const void *src; size_t count; void *dst; } tables[] = {
+    {HW.win.data(), HW.win.size(), &D.win}, {HW.tri_rec.data(), HW.tri_rec.size(), &D.wtri_rec}, {HW.tri_D.data(), HW.tri_D.size(), &D.wtri_D},
+    {HW.bend_rec.data(), HW.bend_rec.size(), &D.wbend_rec}, {HW.bend_w.data(), HW.bend_w.size(), &D.wbend_w},
+    {HW.tri_Dlo.data(), HW.tri_Dlo.size(), &D.wtri_Dlo}, {HW.bend_lo.data(), HW.bend_lo.size(), &D.wbend_lo},
+    {HW.inc.data(), HW.inc.size(), &D.winc}, {HW.inc_ptr.data(), HW.inc_ptr.size(), &D.winc_ptr}, {HW.inc_n.data(), HW.inc_n.size(), &D.winc_n},
+    {HP.pk.data(), HP.pk.size(), &D.pk}, {HP.pk_ptr.data(), HP.pk_ptr.size(), &D.pk_ptr}, {HP.pk_n.data(), HP.pk_n.size(), &D.pk_n},
+    {HP.sq_dinv.data(), HP.sq_dinv.size(), &D.sq_dinv}};
+  static_assert(sizeof(int) == 4 && sizeof(float) == 4, "4-byte table elements");
+  int rc;
+  for (const auto &t : tables) {
+    int *p = nullptr;
+    if ((rc = dev_alloc(c, cl.allocs, &p, t.count))) return rc;
+    if (t.count) HIPCHK(c, hipMemcpy(p, t.src, t.count * 4, hipMemcpyHostToDevice));
+    std::memcpy(t.dst, &p, sizeof(p));
   }
-  D.nb = cl.nb;
-  cl.xch_bytes = (size_t) cl.nb * K * 2 * D.xch_stride * sizeof(v4i);
-  if ((rc = dev_alloc(c, cl.allocs, &D.xch, cl.xch_bytes / sizeof(v4i)))) return rc;
+  if ((rc = dev_alloc(c, cl.allocs, &D.xch, P.xch_bytes / sizeof(v4i)))) return rc;
   if ((rc = dev_alloc(c, cl.allocs, &D.err, 4))) return rc;
   if ((rc = dev_alloc(c, cl.allocs, &D.self_path, 2 * (size_t) c->B))) return rc;
   DevCluster *dD = nullptr;
   if ((rc = dev_alloc(c, cl.allocs, &dD, 1))) return rc;
   D.self_dev = dD;
   HIPCHK(c, hipMemcpy(dD, &D, sizeof(DevCluster), hipMemcpyHostToDevice));
+  cl.K = P.K; cl.nb = P.nb; cl.xch_bytes = P.xch_bytes;
   cl.ok = true;
   return DC_OK;
 }
@@ -354,39 +279,19 @@ static void set_decisions(DevSystem &S, const HostTables &plan) {
   S.max_radii = plan.max_radii; S.self_cap = plan.self_cap; S.self_lds = plan.self_lds;
 }
 
-// K for this batch: enough parts to give every CU a workgroup (B rollouts x K <= CUs, K <= 8), at least as many as a mesh too
-// large for the one-workgroup kernel needs; DC_CLUSTER=k forces k (development switch; 0 / 1 = off).
+// The split of this batch (dc_clusterplan.h): the development switches are read here, once per dc_alloc_batch; DC_CLUSTER=k forces k parts
+// (0 / 1 = off).
 int choose_cluster(dc_ctx *c) {
   free_cluster(c);
-  if (c->host_only || c->B <= 0) return DC_OK;
-  const int forced = env_int("DC_CLUSTER", -1);
-  if (forced == 0 || forced == 1) return DC_OK;
-  if (c->S.dense_inv) { if (forced < 2) return DC_OK; }     // small meshes: the explicit-inverse kernels are the faster ones
-  // Fewer rollouts than CUs: as many parts as fit (B K <= CUs), up to 8 — a rollout's speed-up grows with K (measured on C4: 1.3 /
-  // 1.9 / 3.0 x at K = 2 / 4 / 8). A mesh too large for one workgroup needs kmin parts; when that oversubscribes the device the
-  // batch runs in several launches and K is the one that wastes the least: score = fraction of the CUs busy x per-CU efficiency.
-  // per-CU efficiency of K parts against one workgroup per rollout, re-measured in round 6 on the C4 workload (bench.py --total-batch 128 / 64 / 32
-  // against 256: 6 032 / 5 031 / 4 003 against 9 880 rollout-steps/s -> 0.61 / 0.51 / 0.405 at K = 2 / 4 / 8; K = 3, 5, 6, 7 interpolated)
-  static const double eff[9] = {0, 1.0, 0.61, 0.56, 0.51, 0.48, 0.45, 0.43, 0.405};
-  const int kmin = (!c->S.pk_ok || !c->S.win_ok) ? std::max(2, std::min(8, (c->host.N + 6143) / 6144)) : 1;
-  int K = 1;
-  if (forced >= 2) K = std::min(forced, 8);
-  else if (c->B <= cluster_capacity(c->cus, std::max(kmin, 2))) { K = std::max(kmin, 2); while (K + 1 <= 8 && c->B <= cluster_capacity(c->cus, K + 1)) K++; }
-  else if (kmin > 1) {
-    double best = -1;
-    for (int k = kmin; k <= 8; k++) {
-      const int nbmax = cluster_capacity(c->cus, k), nchunks = (c->B + nbmax - 1) / nbmax, nb = (c->B + nchunks - 1) / nchunks;
-      const double score = (double) nb * k / c->cus * eff[k];
-      if (score > best + 1e-9) { best = score; K = k; }
-    }
-  }
-  for (; K >= 2; K--) {
-    int rc = build_cluster(c, K, forced >= 2);
-    if (rc) return rc;
-    if (c->cl.ok) break;
-    if (forced < 2 && K <= kmin) break;
-  }
-  return DC_OK;
+  ClusterSwitches sw;
+  sw.forced = env_int("DC_CLUSTER", -1);
+  sw.redundant_self = env_on("DC_SELF_REDUNDANT", true);
+  sw.spin_ms = env_int("DC_TEST_SPIN_MS", 0);                  // test hooks
+  sw.test_drop = env_on("DC_TEST_DROP_PART", false);
+  sw.test_skew = env_int("DC_TEST_SKEW_PART", -1);
+  ClusterPlan plan;
+  plan.build(c->host, c->bandwidth, c->B, c->cus, c->host_only, c->S.pk_ok != 0, c->S.win_ok != 0, c->S.dense_inv != nullptr, sw);
+  return plan.ok ? upload_cluster(c, plan) : DC_OK;
 }
 
 // The error word of the split kernels is sticky on the device: it is zero until an exchange times out and is cleared only AFTER that

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #define DC_KERNEL_TU
 #include "dc_devlib.h"
+#include "dc_env.h"
 #include "dc_winlib.h"
 
 namespace dc {
@@ -186,11 +187,7 @@ static int pick_threads_fwd(int N) { return N <= 1536 ? 256 : (N <= 6144 ? 512 :
 // "0" / "1" force the ELL resident kernel (dc_forward_res.hip) in one of its two thread shapes. Default: the
 // packet resident kernel (dc_forward_pk.hip) when its tables exist, else ELL resident, else global.
 static int fwd_variant() {
-  static int v = -3;
-  if (v == -3) {
-    const char *e = getenv("DC_FWD_VARIANT");
-    v = !e ? -2 : (e[0] == 'g' ? -1 : atoi(e));
-  }
+  static const int v = !env_set("DC_FWD_VARIANT") ? -2 : (getenv("DC_FWD_VARIANT")[0] == 'g' ? -1 : env_int("DC_FWD_VARIANT", -2));
   return v;
 }
 

@@ -13,6 +13,7 @@
 // All parts take identical control-flow decisions: every scalar that steers a loop is a sum over the parts in part order.
 #define DC_KERNEL_TU
 #include "dc_forward_cl_kernel.h"
+#include "dc_env.h"
 
 namespace dc {
 
@@ -29,7 +30,7 @@ hipError_t launch_pd_step_cluster(const DevSystem &S, const DevCluster &CL, cons
   // per iteration but carried A r, A p, A s by vector recurrences that drift in fp32 (7e-5 on positions at N = 16 384, docs/HISTORY.md);
   // here no vector is recurred.
   if (S.defl_u && S.fwd_defl) return launch_pd_step_cluster_deflated(S, CL, W, A, b0, nb, st);
-  static const bool sx = !(getenv("DC_SXCG") && getenv("DC_SXCG")[0] == '0');
+  static const bool sx = env_not_off("DC_SXCG", true);
 #define DC_CL_CASE(V) case V: if (sx) return A.inline_detect ? launch_cl_inst<V, true, true>(S, CL, W, A, b0, nb, st) : launch_cl_inst<V, false, true>(S, CL, W, A, b0, nb, st); \
                               return A.inline_detect ? launch_cl_inst<V, true, false>(S, CL, W, A, b0, nb, st) : launch_cl_inst<V, false, false>(S, CL, W, A, b0, nb, st);
   switch (CL.pk_vpt) {

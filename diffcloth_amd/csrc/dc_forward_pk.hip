@@ -21,6 +21,7 @@
 // this PCG on the correction system (see dc_forward.hip header).
 #define DC_KERNEL_TU
 #include "dc_forward_pk_kernel.h"
+#include "dc_env.h"
 
 namespace dc {
 
@@ -30,7 +31,7 @@ bool launch_pd_step_packet_deflated(const DevSystem &S, const DevWork &W, const 
 bool launch_pd_step_packet(const DevSystem &S, const DevWork &W, const FwdArgs &A, int B, hipStream_t st) {
   if (!S.pk_ok) return false;
   if (S.defl_u && S.fwd_defl) return launch_pd_step_packet_deflated(S, W, A, B, st);
-  static const int h16 = getenv("DC_PK_H16") ? atoi(getenv("DC_PK_H16")) : 1;      // (development switch: 0 = the fp32 direction planes)
+  const int h16 = pk_h16_enabled();      // (development switch DC_PK_H16, dc_env.h)
   if (S.pk_threads == 768) {
     if (S.pk_vpt != 14) return false;
     if (h16 && S.win_ok) launch_pk_h16<768, 14, 7>(S, W, A, B, st);

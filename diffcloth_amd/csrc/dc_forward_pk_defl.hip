@@ -4,6 +4,7 @@
 // PD iteration). Reference: the global solve of Simulation::step, Simulation.cpp:1267.
 #define DC_KERNEL_TU
 #include "dc_forward_pk_kernel.h"
+#include "dc_env.h"
 
 namespace dc {
 
@@ -15,7 +16,7 @@ static void launch_deflated(const DevSystem &S, const DevWork &W, const FwdArgs 
 
 bool launch_pd_step_packet_deflated(const DevSystem &S, const DevWork &W, const FwdArgs &A, int B, hipStream_t st) {
   if (!S.pk_ok || !S.defl_u || S.pk_threads != 512) return false;
-  static const int h16 = getenv("DC_PK_H16") ? atoi(getenv("DC_PK_H16")) : 1;
+  const int h16 = pk_h16_enabled();
   switch (S.pk_vpt) {
     case 4: launch_deflated<4, 0>(S, W, A, B, st); break;
     case 6: launch_deflated<6, 0>(S, W, A, B, st); break;

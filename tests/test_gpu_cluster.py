@@ -140,6 +140,56 @@ def test_batch_sizes_that_do_not_fill_whole_xcds_keep_every_workgroup_resident()
     np.testing.assert_array_equal(ga[0], gb[0])
 
 
+# dc_get_cluster (workgroups per rollout, rollouts per launch) per batch size on a 256-CU MI355X, as the engine answered before the split plan
+# moved out of it (csrc/dc_clusterplan.cpp): written down from that engine's choose_cluster / build_cluster compiled unchanged against a stand-in
+# context for 256 CUs, fed the meshes as dc_set_mesh / dc_build leave them (the T-shirt renumbered: bandwidth 155, packet tables and windows, no
+# explicit inverse) — no GPU was free to ask the old library itself. The last entry of each mesh is B = 8 under DC_CLUSTER=4.
+CLUSTER_BATCHES = (1, 8, 32, 33, 40, 64, 200)
+CLUSTER_TABLE = {
+    "grid48": [(8, 1), (8, 8), (8, 32), (6, 33), (6, 40), (4, 64), (1, 200), (4, 8)],
+    "tshirt": [(6, 1), (6, 8), (6, 32), (6, 33), (6, 40), (4, 64), (1, 200), (4, 8)],
+}
+
+
+def tshirt_engine():
+    import scenes
+    V, F = scenes.load_mesh("tshirt")
+    cfg = scenes.TSHIRT
+    P, rmin, rmax = scenes.normalise_model(V, cfg["orientation"], cfg["cloth_dim"])
+    e = capi.Engine(0)
+    e.set_mesh(P, F)
+    e.set_attachments(scenes.corner_attachments(P, rmin, rmax))
+    e.set_params(time_step=cfg["h"], density=cfg["density"], k_stretch=cfg["k_stretch"], k_bend=cfg["k_bend"], forward_tol=cfg["fwd_tol"],
+                 backward_tol=cfg["bwd_tol"], selfcollision_enabled=1, contact_enabled=1)
+    e.build()
+    return e
+
+
+@pytest.mark.parametrize("mesh", ["grid48", "tshirt"])
+def test_cluster_choice_per_batch_size_is_the_recorded_one(mesh):
+    """Allocation only: for the 48 x 48 cloth and the 1 426-vertex T-shirt, every batch size of CLUSTER_BATCHES (and B = 8 with DC_CLUSTER=4) gets
+    the K and the launch size the engine chose before its split plan became host-side code of its own, and every launch keeps its workgroups
+    resident: ceil(rollouts per launch / 8) * K workgroups on the 32 CUs of one XCD."""
+    import ctypes
+    e = sphere_scene(48)[2] if mesh == "grid48" else tshirt_engine()
+    lib = capi.load_library()
+    got = []
+    for forced, B in [(None, b) for b in CLUSTER_BATCHES] + [(4, 8)]:
+        if forced is None:
+            e.alloc_batch(B, 1)
+        else:
+            with cluster_env(forced):
+                e.alloc_batch(B, 1)
+        k_c, nb_c = ctypes.c_int(), ctypes.c_int()
+        assert lib.dc_get_cluster(e.h, ctypes.byref(k_c), ctypes.byref(nb_c)) == 0
+        assert e.cluster() == k_c.value
+        per_xcd = -(-nb_c.value // 8) * k_c.value
+        print(f"\n[cluster table] {mesh} B={B} DC_CLUSTER={forced}: K={k_c.value}, {nb_c.value} rollouts per launch -> {per_xcd} workgroups per XCD")
+        assert per_xcd <= 32
+        got.append((k_c.value, nb_c.value))
+    assert got == CLUSTER_TABLE[mesh]
+
+
 def test_split_agrees_with_one_workgroup_per_rollout():
     """Same inputs through K = 1 and K = 4: different summation order, same answer to solver tolerance; parameter gradients too."""
     B, S = 4, 3

@@ -30,6 +30,20 @@ def test_record_import_lays_out_the_callers_self_contacts(tmp_path):
     assert r.returncode == 0 and r.stdout.strip().endswith("ALL OK"), r.stdout + r.stderr
 
 
+def test_cluster_plan_keeps_every_workgroup_resident_and_refuses_what_does_not_fit(tmp_path):
+    """csrc/dc_clusterplan.cpp, the host-side plan of the split execution (tests/native/cluster_plan_check.cpp): for every batch size 1 ... 300 on
+    256, 304 and 64 CUs the workgroups of a launch fit one XCD's CUs and the launches cover the batch; every rejection of the per-K search on the
+    smallest grid that triggers it; the shape of an accepted plan; the K walk, the early returns and the switches — against answers worked out by
+    hand or written down from the engine before the plan was moved out of it."""
+    csrc = os.path.join(ROOT, "diffcloth_amd", "csrc")
+    exe = str(tmp_path / "cluster_plan_check")
+    srcs = [os.path.join(ROOT, "tests", "native", "cluster_plan_check.cpp")] + [os.path.join(csrc, f) for f in ("dc_clusterplan.cpp", "dc_system.cpp", "dc_windows.cpp", "dc_packets.cpp")]
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", "-Wall", "-I", csrc, "-o", exe] + srcs)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ALL OK"), r.stdout + r.stderr
+
+
 def test_deflation_builder_finds_the_lowest_eigenvectors(tmp_path):
     """csrc/dc_deflate.cpp on a synthetic badly graded strip (cells shrinking 100 x across the sheet): the Chebyshev-filtered subspace
     iteration returns orthonormal vectors whose eigen-residuals |A u - theta u| are small, (U^T A U)^-1 is consistent, in well under a
