@@ -23,6 +23,7 @@
 #include "dc_denselib.h"
 #include "dc_adjprecond.h"
 #include "dc_adjoint64.h"
+#include "dc_launch.h"
 
 namespace dc {
 
@@ -654,54 +655,6 @@ __device__ DC_OUTLINED Ret32 cg32_solve(const DevSystem &S, AdjCtx C, Krylov32 V
   return Ret32{in_status, kdone + (its + 1) / 2, its, rr};      // (iters = the CG iterations of this solve)
 }
 
-// The contact vertices' y list (AdjCtx::ylist) in what the windows leave of the CU's LDS — for the 1024-thread kernels, which have their CU to
-// themselves at 128 registers per lane whatever their LDS (4 waves per SIMD): the larger request costs no mesh a second workgroup per CU.
-// Returns the bytes to add to the launch's dynamic LDS and sets A.ycap.
-// `lds_limit` = what the device grants a workgroup (hipDeviceAttributeMaxSharedMemoryPerBlock), `static_lds` = the instance's own static LDS
-// (hipFuncGetAttributes::sharedSizeBytes): both queried, not assumed — see adj_lds_budget below.
-template <int THREADS>
-static size_t ylist_room(const DevSystem &S, size_t lds, BwdArgs &A, size_t lds_limit, size_t static_lds) {
-  A.ycap = 0; A.ybase = (int) (lds / 4);
-  const size_t reserve = static_lds + 256;
-  if (THREADS != 1024 || lds + reserve + 12 > lds_limit) return 0;
-  const size_t room = lds_limit - reserve - lds;
-  A.ycap = (int) std::min(room / 12, (size_t) S.N + 2 * (size_t) S.self_cap);
-  return (size_t) A.ycap * 12;
-}
-// LDS limit of the current device and static LDS of a kernel instance, each queried once per (device, instance)
-struct AdjLdsBudget { size_t limit, static_lds; bool ok; };
-static AdjLdsBudget adj_lds_budget(const void *func, int dev) {
-  AdjLdsBudget b{(size_t) 64 * 1024, (size_t) 4096, false};
-  int v = 0;
-  if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && v > 0) b.limit = (size_t) v;
-  // (a workgroup may be granted the whole CU's LDS through hipFuncAttributeMaxDynamicSharedMemorySize: 160 KB on gfx950)
-  if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) == hipSuccess && (size_t) v > b.limit) b.limit = (size_t) v;
-  hipFuncAttributes fa;
-  if (hipFuncGetAttributes(&fa, func) == hipSuccess) { b.static_lds = fa.sharedSizeBytes; b.ok = true; }
-  return b;
-}
-// Configures the instance's dynamic LDS for this launch: windows (`lds`) + the y list in what is left. When the device refuses the larger
-// request the launch goes without the list (ycap = 0) instead of failing without a diagnosis.
-template <int THREADS>
-static size_t adj_configure_lds(const void *func, const DevSystem &S, size_t lds, BwdArgs &Ay, size_t (&configured)[kMaxDevices], AdjLdsBudget (&budget)[kMaxDevices]) {
-  int dev = 0;
-  (void) hipGetDevice(&dev);
-  const int slot = dev >= 0 && dev < kMaxDevices ? dev : 0;
-  if (!budget[slot].ok || dev >= kMaxDevices) budget[slot] = adj_lds_budget(func, dev);
-  const size_t base = lds;
-  lds += ylist_room<THREADS>(S, lds, Ay, budget[slot].limit, budget[slot].static_lds);
-  size_t &done = configured[slot];
-  if (lds > done || dev >= kMaxDevices) {
-    if (hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds) == hipSuccess) done = lds;
-    else {
-      (void) hipGetLastError();
-      Ay.ycap = 0; lds = base;
-      if (lds > done) { if (hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds) == hipSuccess) done = lds; }
-    }
-  }
-  return lds;
-}
-
 // BLK: direct solve preconditioned with K's own 3 x 3 diagonal blocks (dc_adjprecond.h) instead of diag(P)^-1
 template <int THREADS, bool WIN, bool DENSE, bool BLK, bool COARSE = false>
 __global__ __launch_bounds__(THREADS) void k_adjoint_step(const DevSystem *__restrict__ Sp, DevWork W, BwdArgs A) {
@@ -1023,27 +976,46 @@ static int pick_threads_bwd(int N) {
   return 1024;
 }
 
+// Launch of a windowed instance with `base` bytes of dynamic LDS (adj_lds_bytes) plus the contact vertices' y list in what that leaves of the
+// CU's LDS (adj_ylist). The device's limit and the instance's static LDS are queried once per (device, instance), not assumed; when the device
+// refuses the larger request the launch goes without the list (ycap = 0) instead of failing without a diagnosis.
+template <auto Kernel, int THREADS>
+static void launch_adj_lds(const DevSystem &S, const DevWork &W, const BwdArgs &A, int B, hipStream_t st, size_t base) {
+  struct Budget { size_t limit, static_lds; bool ok; };
+  static Budget budget[kMaxDevices] = {};
+  int dev = 0;
+  (void) hipGetDevice(&dev);
+  Budget &b = budget[dev >= 0 && dev < kMaxDevices ? dev : 0];
+  if (!b.ok || dev >= kMaxDevices) {
+    b = Budget{(size_t) 64 * 1024, (size_t) 4096, false};
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && v > 0) b.limit = (size_t) v;
+    // (a workgroup may be granted the whole CU's LDS through hipFuncAttributeMaxDynamicSharedMemorySize: 160 KB on gfx950)
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) == hipSuccess && (size_t) v > b.limit) b.limit = (size_t) v;
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, (const void *) Kernel) == hipSuccess) { b.static_lds = fa.sharedSizeBytes; b.ok = true; }
+  }
+  const AdjYlist y = adj_ylist(THREADS, base, b.limit, b.static_lds, S.N, S.self_cap);
+  BwdArgs Ay = A;
+  Ay.ycap = y.ycap; Ay.ybase = y.ybase;
+  size_t lds = y.bytes;
+  if (ensure_dynamic_lds<Kernel>(lds) != hipSuccess) {
+    (void) hipGetLastError();
+    Ay.ycap = 0; lds = base;
+    (void) ensure_dynamic_lds<Kernel>(lds);      // (refused as well: the launch reports it)
+  }
+  hipLaunchKernelGGL(Kernel, dim3(B), dim3(THREADS), lds, st, S.self_dev, W, Ay);
+}
 template <int THREADS, bool DENSE, bool BLK>
 static void launch_adj_b(const DevSystem &S, const DevWork &W, const BwdArgs &A, int B, hipStream_t st) {
   if (!S.win_ok) { hipLaunchKernelGGL((k_adjoint_step<THREADS, false, false, false>), dim3(B), dim3(THREADS), 0, st, S.self_dev, W, A); return; }
-  size_t lds = (size_t) S.win_lds_bytes;
-  if (DENSE) lds = std::max(lds, sizeof(float) * (size_t) (3 * S.dense_ld + dense_lds_floats(S.dense_ld, THREADS / 64)));
-  BwdArgs Ay = A;
-  static size_t configured[kMaxDevices] = {};        // the attribute is per device: one entry per device this process has used
-  static AdjLdsBudget budget[kMaxDevices] = {};
-  lds = adj_configure_lds<THREADS>((const void *) k_adjoint_step<THREADS, true, DENSE, BLK>, S, lds, Ay, configured, budget);
-  hipLaunchKernelGGL((k_adjoint_step<THREADS, true, DENSE, BLK>), dim3(B), dim3(THREADS), lds, st, S.self_dev, W, Ay);
+  launch_adj_lds<k_adjoint_step<THREADS, true, DENSE, BLK>, THREADS>(S, W, A, B, st, adj_lds_bytes(THREADS, true, S.win_lds_bytes, DENSE, S.dense_ld, false));
 }
 // the instances with the coarse level of the preconditioner (meshes the engine built a deflation space for, direct solve, block preconditioner):
 // kernels of their own — inlined next to the plain solve the coarse code cost the headline's adjoint 4 % without ever running
 template <int THREADS>
 static void launch_adj_coarse(const DevSystem &S, const DevWork &W, const BwdArgs &A, int B, hipStream_t st) {
-  size_t lds = std::max((size_t) S.win_lds_bytes, sizeof(float) * (size_t) kCoarseLdsFloats);
-  BwdArgs Ay = A;
-  static size_t configured[kMaxDevices] = {};
-  static AdjLdsBudget budget[kMaxDevices] = {};
-  lds = adj_configure_lds<THREADS>((const void *) k_adjoint_step<THREADS, true, false, true, true>, S, lds, Ay, configured, budget);
-  hipLaunchKernelGGL((k_adjoint_step<THREADS, true, false, true, true>), dim3(B), dim3(THREADS), lds, st, S.self_dev, W, Ay);
+  launch_adj_lds<k_adjoint_step<THREADS, true, false, true, true>, THREADS>(S, W, A, B, st, adj_lds_bytes(THREADS, true, S.win_lds_bytes, false, S.dense_ld, true));
 }
 template <int THREADS, bool DENSE>
 static void launch_adj(const DevSystem &S, const DevWork &W, const BwdArgs &A, int B, hipStream_t st) {

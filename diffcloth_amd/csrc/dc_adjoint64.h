@@ -15,6 +15,7 @@
 #pragma once
 #include "dc_devlib.h"
 #include "dc_adjprecond.h"
+#include "dc_launchplan.h"      // kCoarseVectors, kCoarseLdsFloats
 
 // Inlined by default: out of line (-DDC_ADJ_OUTLINE, A/B builds) the fp32 correction solve pays the call ABI — measured r03a on the
 // 10k-vertex workload: 45.8 ms per fwd+bwd batch step out of line against 35.6 ms inlined.
@@ -446,8 +447,6 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
 }
 
-constexpr int kCoarseVectors = 16;
-constexpr int kCoarseLdsFloats = 2 * (16 * 3 * kCoarseVectors + 3 * kCoarseVectors);      // scratch of precondition64 in floats (16 = waves or parts, at most)
 template <int THREADS, class Team>
 __device__ __forceinline__ bool precondition64(const DevSystem &S, Team &tm, const float *__restrict__ minv, const double *src, double *dst, float *lds) {
   const int N = S.N, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;

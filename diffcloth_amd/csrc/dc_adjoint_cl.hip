@@ -16,6 +16,7 @@
 #include "dc_cluster.h"
 #include "dc_adjprecond.h"
 #include "dc_adjoint64.h"
+#include "dc_launch.h"
 #include <algorithm>
 
 #ifdef DC_PROFILE_PHASES
@@ -598,26 +599,20 @@ __global__ __launch_bounds__(THREADS) void k_adjoint_step_cl(const DevSystem *__
 #ifndef DC_ADJ_CL_THREADS
 #define DC_ADJ_CL_THREADS 512      // round 6: 512 threads x 256 registers (241 spilled VGPRs, 556 B scratch) instead of 1024 x 128 (855 / 1 144 B): -8 % per step
 #endif
-hipError_t launch_adjoint_step_cluster(const DevSystem &S, const DevCluster &CL, const DevWork &W, const BwdArgs &A, int b0, int nb, hipStream_t st) {
+template <bool BLK, bool COARSE>
+static hipError_t launch_adj_cl_inst(const DevSystem &S, const DevCluster &CL, const DevWork &W, const BwdArgs &A, int b0, int nb, hipStream_t st) {
   constexpr int THREADS = DC_ADJ_CL_THREADS;
-  const int hc_off = (CL.win_lds_bytes / 4 + 3) / 4 * 4;
-  const int tail_off = hc_off + 6 * CL.HB;
-  const size_t lds = sizeof(float) * (size_t) (tail_off + kXchLdsFloats);
-  if (lds > 160 * 1024 - 256 || A.mode != 1) return hipErrorInvalidValue;
-  if (A.block_pre && S.adj_coarse && S.defl_u) {      // the fall-back with the coarse level: an instance of its own (dc_adjoint.hip launch_adj_coarse)
-    hipError_t e = hipFuncSetAttribute((const void *) k_adjoint_step_cl<THREADS, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_adjoint_step_cl<THREADS, true, true>), dim3((nb + 7) / 8 * 8 * CL.K), dim3(THREADS), lds, st, S.self_dev, CL.self_dev, W, A, b0, nb, hc_off, tail_off);
-  } else if (A.block_pre) {
-    hipError_t e = hipFuncSetAttribute((const void *) k_adjoint_step_cl<THREADS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_adjoint_step_cl<THREADS, true>), dim3((nb + 7) / 8 * 8 * CL.K), dim3(THREADS), lds, st, S.self_dev, CL.self_dev, W, A, b0, nb, hc_off, tail_off);
-  } else {
-    hipError_t e = hipFuncSetAttribute((const void *) k_adjoint_step_cl<THREADS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_adjoint_step_cl<THREADS, false>), dim3((nb + 7) / 8 * 8 * CL.K), dim3(THREADS), lds, st, S.self_dev, CL.self_dev, W, A, b0, nb, hc_off, tail_off);
-  }
+  const ClAdjointLds l = cl_adjoint_lds(CL.HB, CL.win_lds_bytes);
+  if (!l.ok || A.mode != 1) return hipErrorInvalidValue;
+  const hipError_t e = ensure_dynamic_lds<k_adjoint_step_cl<THREADS, BLK, COARSE>>(l.bytes);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((k_adjoint_step_cl<THREADS, BLK, COARSE>), dim3((nb + 7) / 8 * 8 * CL.K), dim3(THREADS), l.bytes, st, S.self_dev, CL.self_dev, W, A, b0, nb, l.hc_off, l.tail_off);
   return hipGetLastError();
+}
+hipError_t launch_adjoint_step_cluster(const DevSystem &S, const DevCluster &CL, const DevWork &W, const BwdArgs &A, int b0, int nb, hipStream_t st) {
+  // (with the coarse level: the fall-back is an instance of its own, dc_adjoint.hip launch_adj_coarse)
+  if (A.block_pre && S.adj_coarse && S.defl_u) return launch_adj_cl_inst<true, true>(S, CL, W, A, b0, nb, st);
+  return A.block_pre ? launch_adj_cl_inst<true, false>(S, CL, W, A, b0, nb, st) : launch_adj_cl_inst<false, false>(S, CL, W, A, b0, nb, st);
 }
 
 }  // namespace dc

@@ -18,10 +18,12 @@
 // never starts more workgroups than the device has CUs).
 #pragma once
 #include "dc_devlib.h"
+#include "dc_launchplan.h"      // kXchWaves, kXchLdsFloats, kSpinLimit, kGranuleBytes
 
 namespace dc {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
+static_assert(sizeof(v4i) == kGranuleBytes, "dc_launchplan.h restates the size of an exchange granule");
 
 struct DevCluster {
   int K;              // workgroups (parts) per rollout
@@ -58,8 +60,6 @@ struct DevCluster {
   const DevCluster *self_dev;
 };
 
-constexpr long long kSpinLimit = 200000000ll;     // 2 s of the 100 MHz wall clock
-
 // ---- sc1 (write-through / L1-bypassing) access to a planar [3][N] vector of one rollout through a buffer resource ----
 // Loads always bypass the L1 (sc1: served by the XCD's L2, or by memory when the line is not there). Stores are write-through
 // (sc1: the line goes to memory and leaves the L2) unless `same_xcd`: when every part of the rollout was found on ONE XCD
@@ -91,7 +91,6 @@ struct In2Sc1 {       // input loader of element_windows_t (stage1 / in2) for a 
 };
 
 // ---- exchange state of one workgroup ----
-constexpr int kXchWaves = 16;          // sum granules per (part, parity): one per wave of the publishing workgroup (<= 1024 threads)
 struct Xch {
   __amdgpu_buffer_rsrc_t rs;    // the rollout's exchange area
   unsigned seq;                 // sequence number of the current exchange (tag); starts at 0 = "nothing yet"
@@ -121,7 +120,6 @@ __device__ __forceinline__ Xch xch_init(const DevCluster &CL, int lb, int part, 
   if (threadIdx.x == 0) *X.ldead = 0;
   return X;
 }
-constexpr int kXchLdsFloats = 32;      // tail of the dynamic LDS the exchange uses (lsum[2][4], ldead, padding; [16, 32): the six-sum totals, two parities of 8)
 
 __device__ __forceinline__ int xch_off(const Xch &X, int part, int g) { return ((part * 2 + (int) (X.seq & 1u)) * X.stride + g) * 16; }
 

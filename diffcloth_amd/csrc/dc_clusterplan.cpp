@@ -11,7 +11,6 @@ bool ClusterPlan::fit(const HostSystem &H, int bandwidth, int Kc, bool forced) {
   if (Kc < 2 || bandwidth <= 0 || bandwidth > 511) return false;
   const int HBc = std::max(64, round64(bandwidth));
   static const int allowed[] = {1, 2, 3, 4, 6, 8, 12};
-  const int lds_cap = kClusterLdsBytes / 4 - cplan::kXchLdsFloats;      // floats
   HostWindows HW;
   int Rf = 0, w_f = 0, vpt = 0;
   for (int w = 1; w <= 8 && Rf == 0; w++) {
@@ -27,9 +26,8 @@ bool ClusterPlan::fit(const HostSystem &H, int bandwidth, int Kc, bool forced) {
     if (v == 0) continue;                                // more rows per part than the kernel holds in registers: more windows do not help
     if (!HW.build_own(H, own_w)) continue;
     const int win_floats = (int) (HW.lds_bytes / 4);
-    const int fwd = std::max(std::max((v <= 6 ? 6 : 3) * (Rc + 2 * HBc), win_floats), cplan::kSelfDetectLdsInts);      // (<= 6 rows per thread: pipelined CG, two gather arrays)
-    const int bwd = (win_floats + 3) / 4 * 4 + 6 * HBc;
-    if (fwd + 4 > lds_cap || bwd + 4 > lds_cap) continue;
+    // both split kernels' dynamic LDS, whichever instance the launchers choose, within the workgroup's limit (dc_launchplan.h)
+    if (!cl_bound_fits(cl_forward_floats_bound(v, Rc, HBc, win_floats)) || !cl_bound_fits(cl_adjoint_floats_bound(HBc, win_floats))) continue;
     // the element reach of every window must stay inside the boundary rows its part receives
     bool reach_ok = true;
     for (int q = 0; q < HW.nwin; q++) {
@@ -43,7 +41,7 @@ bool ClusterPlan::fit(const HostSystem &H, int bandwidth, int Kc, bool forced) {
   if (Rf == 0) return false;
   HostPackets HP;
   if (!HP.build_rows(H, Kc * Rf)) return false;
-  K = Kc; R = Rf; HB = HBc; wpp = w_f; pk_vpt = vpt; xch_stride = cplan::kXchWaves + 2 * HBc;
+  K = Kc; R = Rf; HB = HBc; wpp = w_f; pk_vpt = vpt; xch_stride = kXchWaves + 2 * HBc;
   win = std::move(HW); pk = std::move(HP);
   return true;
 }
@@ -82,7 +80,7 @@ void ClusterPlan::build(const HostSystem &H, int bandwidth, int B, int cus, bool
     const int nbmax = cluster_capacity(cus, K), nchunks = (B + nbmax - 1) / nbmax;
     nb = std::max(1, (B + nchunks - 1) / nchunks);
   }
-  xch_bytes = (size_t) nb * K * 2 * xch_stride * cplan::kGranuleBytes;
+  xch_bytes = (size_t) nb * K * 2 * xch_stride * kGranuleBytes;
   redundant_self = sw.redundant_self; test_drop = sw.test_drop; test_skew = sw.test_skew;
   if (sw.spin_ms > 0) spin_limit = (long long) sw.spin_ms * 100000ll;      // test hook
 }

@@ -6,23 +6,17 @@
 #pragma once
 #include <cstddef>
 #include <vector>
+#include "dc_launchplan.h"
 #include "dc_packets.h"
 #include "dc_system.h"
 #include "dc_windows.h"
 
 namespace dc {
 
-namespace cplan {
-// dc_cluster.h's kXchWaves / kXchLdsFloats / kSpinLimit, dc_selftmp.h's kSelfDetectLdsInts and the size of an exchange granule (v4i)
-// under names of their own (those headers need the HIP compiler); dc_engine.hip asserts that they agree
-constexpr int kXchWaves = 16;
-constexpr int kXchLdsFloats = 32;
-constexpr long long kSpinLimit = 200000000ll;
-constexpr int kSelfDetectLdsInts = 16 + (4096 + 1) + 4096 + 1 + 2048;
-constexpr int kGranuleBytes = 16;
+namespace cplan {      // the exchange's sizes (dc_launchplan.h) under the names this plan's check knows them by
+using dc::kXchWaves;
+using dc::kSpinLimit;
 }  // namespace cplan
-
-constexpr int kClusterLdsBytes = 160 * 1024 - 256;   // dynamic LDS a workgroup of the split kernels may ask for (the exchange's tail included)
 
 // values of the development switches dc_alloc_batch reads (defaults: nothing forced, no test hook)
 struct ClusterSwitches {
@@ -47,7 +41,7 @@ struct ClusterPlan {
   int xch_stride = 0;           // granules per (part, parity)
   int nb = 0;                   // rollouts per launch: all B when they fit, else equal chunks
   size_t xch_bytes = 0;         // exchange area of one launch
-  long long spin_limit = cplan::kSpinLimit;
+  long long spin_limit = kSpinLimit;
   int redundant_self = 1, test_drop = 0, test_skew = -1;
   HostWindows win;              // windows of R / wpp owned vertices
   HostPackets pk;               // packet matrix padded to K R rows

@@ -2,17 +2,9 @@
 // rollout, x in LDS, the matrix (batch-shared, L2 resident) streamed once per product.
 #pragma once
 #include "dc_devlib.h"
+#include "dc_launchplan.h"      // dense_chunks, dense_lds_floats
 
 namespace dc {
-
-// number of column chunks the product is split into so that every wave of the workgroup has ~4 (row group, chunk) units
-__host__ __device__ __forceinline__ int dense_chunks(int ld, int waves) {
-  const int R = ld >> 6;
-  int C = (4 * waves + R - 1) / R;
-  return C < 1 ? 1 : (C > 8 ? 8 : C);
-}
-// floats of LDS the partial sums need
-__host__ __device__ __forceinline__ int dense_lds_floats(int ld, int waves) { return 3 * ld * dense_chunks(ld, waves); }
 
 // Partial products: unit (row group rw, chunk c) = rows 64 rw .. 64 rw + 63 against columns [c JC, (c + 1) JC), one wave
 // per unit, lane = row. The matrix is symmetric, so "row i, column j" is read as inv[j * ld + i]: the 64 lanes of a wave

@@ -27,8 +27,6 @@ constexpr int kMetaStride = 4096;
 #define DC_C
 #endif
 
-constexpr int kMaxDevices = 64;       // launchers cache per-device kernel attributes
-
 struct DevPrim {
   int kind, group, rotates, pad;
   float cx, cy, cz, radius;

@@ -25,8 +25,6 @@ hipError_t launch_adjoint_step_cluster(const DevSystem &S, const DevCluster &CL,
 static_assert(rec::kMetaStride == kMetaStride && rec::kMaxLayers == kMaxLayers, "dc_record.h restates dc_device.h's record sizes");
 static_assert(sizeof(rec::Int2) == sizeof(int2) && alignof(rec::Int2) == alignof(int2), "dc_record.h: Int2 is uploaded as int2");
 static_assert(sizeof(rec::Float4) == sizeof(float4) && alignof(rec::Float4) == alignof(float4), "dc_record.h: Float4 is uploaded as float4");
-static_assert(cplan::kXchWaves == kXchWaves && cplan::kXchLdsFloats == kXchLdsFloats && cplan::kSpinLimit == kSpinLimit, "dc_clusterplan.h restates dc_cluster.h's exchange sizes");
-static_assert(cplan::kSelfDetectLdsInts == kSelfDetectLdsInts && cplan::kGranuleBytes == sizeof(v4i), "dc_clusterplan.h restates dc_selftmp.h's LDS need and the granule size");
 
 namespace {
 

@@ -6,6 +6,7 @@
 #include "dc_selflib.h"
 #include "dc_pklib.h"
 #include "dc_cluster.h"
+#include "dc_launch.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -769,16 +770,11 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_cl(const DevSystem *__restr
 template <int VPT, bool DETECT, bool PIPE, bool DEFL = false>
 static hipError_t launch_cl_inst(const DevSystem &S, const DevCluster &CL, const DevWork &W, const FwdArgs &A, int b0, int nb, hipStream_t st) {
   constexpr int THREADS = 512;
-  const int GL = CL.R + 2 * CL.HB;
-  int floats = std::max((PIPE ? 2 : 3) * GL + (PIPE ? 6 * CL.HB : 0), CL.win_lds_bytes / 4);      // (PIPE: direction as 8-byte rows + the neighbours' residual rows)
-  const int fric_floats = floats;      // LDS offered to the layered friction pass: the same with and without the inlined detection
-  if (DETECT) floats = std::max(floats, kSelfDetectLdsInts);
-  const int tail_off = (floats + 3) / 4 * 4;
-  const size_t lds = sizeof(float) * (size_t) (tail_off + kXchLdsFloats);
-  if (lds > 160 * 1024 - 256 - (DEFL ? 512 : 0)) return hipErrorInvalidValue;      // (DEFL: 384 bytes of static LDS)
-  hipError_t e = hipFuncSetAttribute((const void *) k_pd_step_cl<THREADS, VPT, DETECT, PIPE, DEFL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+  const ClForwardLds l = cl_forward_lds(CL.R, CL.HB, CL.win_lds_bytes, PIPE, DETECT, DEFL);
+  if (!l.ok) return hipErrorInvalidValue;
+  const hipError_t e = ensure_dynamic_lds<k_pd_step_cl<THREADS, VPT, DETECT, PIPE, DEFL>>(l.bytes);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_pd_step_cl<THREADS, VPT, DETECT, PIPE, DEFL>), dim3((nb + 7) / 8 * 8 * CL.K), dim3(THREADS), lds, st, S.self_dev, CL.self_dev, W, A, b0, nb, tail_off, fric_floats);
+  hipLaunchKernelGGL((k_pd_step_cl<THREADS, VPT, DETECT, PIPE, DEFL>), dim3((nb + 7) / 8 * 8 * CL.K), dim3(THREADS), l.bytes, st, S.self_dev, CL.self_dev, W, A, b0, nb, l.tail_off, l.fric_floats);
   return hipGetLastError();
 }
 

@@ -7,6 +7,7 @@
 #include "dc_denselib.h"
 #include "dc_selflib.h"
 #include "dc_pklib.h"
+#include "dc_launch.h"
 #include <algorithm>
 
 
@@ -684,18 +685,8 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_pk(const DevSystem *__restr
 
 template <int THREADS, int VPT, int XL, bool DETECT, bool DENSE, bool H16 = false, bool DEFL = false>
 static void launch_pk_inst(const DevSystem &S, const DevWork &W, const FwdArgs &A, int B, hipStream_t st) {
-  size_t lds = (size_t) THREADS * ((H16 ? 2 : 3) * VPT + 3 * XL) * sizeof(float);
-  if (DENSE) lds += sizeof(float) * (size_t) dense_lds_floats(S.dense_ld, THREADS / 64);
-  if (S.win_ok) lds = std::max(lds, (size_t) S.win_lds_bytes);
-  if (A.inline_detect) lds = std::max(lds, sizeof(int) * (size_t) kSelfDetectLdsInts);
-  static size_t configured[kMaxDevices] = {};        // the attribute is per device: one entry per device this process has used
-  int dev = 0;
-  (void) hipGetDevice(&dev);
-  size_t &done = configured[dev >= 0 && dev < kMaxDevices ? dev : 0];
-  if (lds > done || dev >= kMaxDevices) {
-    (void) hipFuncSetAttribute((const void *) k_pd_step_pk<THREADS, VPT, XL, DETECT, DENSE, H16, DEFL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-    done = lds;
-  }
+  const size_t lds = pk_lds_bytes(THREADS, VPT, XL, H16, DENSE, S.dense_ld, S.win_ok, S.win_lds_bytes, A.inline_detect);
+  (void) ensure_dynamic_lds<k_pd_step_pk<THREADS, VPT, XL, DETECT, DENSE, H16, DEFL>>(lds);      // (refused: the launch reports it)
   hipLaunchKernelGGL((k_pd_step_pk<THREADS, VPT, XL, DETECT, DENSE, H16, DEFL>), dim3(B), dim3(THREADS), lds, st, S.self_dev, W, A);
 }
 

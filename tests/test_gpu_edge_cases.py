@@ -252,3 +252,46 @@ def test_two_contexts_agree_bit_for_bit_with_self_contacts():
     for other in res[1:]:
         for a, b in zip(res[0], other):
             assert np.array_equal(a, b)
+
+
+def test_dynamic_lds_grant_of_a_kernel_instance_serves_two_meshes_in_one_process(monkeypatch):
+    """The launchers remember, per device and kernel instance, the dynamic LDS the runtime has granted (csrc/dc_launch.h). Two grids with two rows
+    per thread of the packet kernel, 24 x 24 and 32 x 32 without the explicit inverse, share every step-kernel instance but differ in their window
+    LDS and in the room of the adjoint's y list: the smaller one steps, the larger one raises the grant and steps, the smaller one steps again under
+    the larger grant — bit for bit what it computed the first time. (DC_CLUSTER=1: one workgroup per rollout, as a full batch gets; a batch of two
+    would be split into parts whose number, and so whose kernel instances, differ between the two grids.)"""
+    monkeypatch.setenv("DC_DENSE_MAX_N", "0")
+    monkeypatch.setenv("DC_CLUSTER", "1")
+    rng = np.random.default_rng(11)
+
+    def context(n):
+        V, F = meshes.grid_cloth(n, n, 4.5, 4.5, "DOWN")
+        V = f32(V)
+        c = f32(meshes.sphere_scene_center(V, 2.0))
+        e = engine(V, F, prims=[dict(kind=capi.DC_PRIM_SPHERE, group=0, center=c, radius=2.0, mu=0.5)], forward_tol=1e-7, selfcollision_enabled=1,
+                   cg_rel_tol=1e-5, adjoint_rel_tol=1e-6)
+        e.alloc_batch(2, 1)
+        x0 = np.stack([f32(V.reshape(-1) + np.tile([rng.uniform(-0.3, 0.3), -0.05, rng.uniform(-0.3, 0.3)], len(V))) for _ in range(2)])
+        g = f32(1e-3 * rng.standard_normal(x0.shape))
+        return e, x0, g
+
+    def step(e, x0, g):
+        e.set_state(0, x0, np.zeros_like(x0))
+        st = e.step_forward(0)
+        x, v = e.get_state(1)
+        gb = e.step_backward(1, g, g)
+        return st, gb, (x, v, gb["dL_dx"], gb["dL_dv"], gb["dL_dmu"])
+
+    small, large = context(24), context(32)
+    kernel_set = [(e[0].layout()["packet_kernel"], e[0].layout()["element_windows"], e[0].layout()["dense_inverse"], e[0].deflation()[0], e[0].cluster()) for e in (small, large)]
+    print(kernel_set, small[0].layout(), large[0].layout())
+    assert kernel_set[0] == kernel_set[1] == (True, True, False, 0, 1)
+    assert (small[0].N + 511) // 512 == (large[0].N + 511) // 512 == 2
+    _, _, first = step(*small)
+    st, gb, out = step(*large)
+    assert np.all(st["converged"] == 1) and np.all(np.isin(gb["converged"], (1, 2))), (st, gb)      # (2: the adjoint stalled at the fp32 floor)
+    assert all(np.isfinite(a).all() for a in out) and np.abs(out[2]).max() > 0
+    _, _, again = step(*small)
+    for a, b in zip(first, again):
+        assert np.array_equal(a, b)
+    assert np.isfinite(first[2]).all() and np.abs(first[2]).max() > 0

@@ -44,6 +44,19 @@ def test_cluster_plan_keeps_every_workgroup_resident_and_refuses_what_does_not_f
     assert r.returncode == 0 and r.stdout.strip().endswith("ALL OK"), r.stdout + r.stderr
 
 
+def test_launch_plan_sizes_offsets_and_limits_of_the_dynamic_lds(tmp_path):
+    """csrc/dc_launchplan.h, the host-side plan of every step kernel's dynamic LDS (tests/native/launch_plan_check.cpp): byte counts, offsets, the
+    y list's room and the refusals at the workgroup's limit against figures written out by hand; the split plan's bounds cover every instance
+    the launchers choose, on a sweep of part shapes and for every plan ClusterPlan::fit accepts with K = 2 ... 8 on three grids."""
+    csrc = os.path.join(ROOT, "diffcloth_amd", "csrc")
+    exe = str(tmp_path / "launch_plan_check")
+    srcs = [os.path.join(ROOT, "tests", "native", "launch_plan_check.cpp")] + [os.path.join(csrc, f) for f in ("dc_clusterplan.cpp", "dc_system.cpp", "dc_windows.cpp", "dc_packets.cpp")]
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-I", csrc, "-o", exe] + srcs)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ALL OK"), r.stdout + r.stderr
+
+
 def test_deflation_builder_finds_the_lowest_eigenvectors(tmp_path):
     """csrc/dc_deflate.cpp on a synthetic badly graded strip (cells shrinking 100 x across the sheet): the Chebyshev-filtered subspace
     iteration returns orthonormal vectors whose eigen-residuals |A u - theta u| are small, (U^T A U)^-1 is consistent, in well under a
