@@ -60,13 +60,15 @@ struct DevSystem {
   const int DC_G *ell_w;             // [ceil(N/64)] width of the chunk
   // P once more, symmetrically scaled to unit diagonal (D^-1/2 P D^-1/2) and packed for dc_forward_pk.hip: per
   // 64-row chunk pk_n[c] 16-byte packets per row (a multiple of 4), packet (s, lane) at pk[pk_ptr[c] + 64 s + lane] =
-  // {v0, v1, v2, d0 | d1 << 10 | d2 << 20}, d = column - row + 512; chunks cover pk_threads * pk_vpt rows
+  // {v0, v1, v2, d0 | d1 << 10 | d2 << 20}, d = column - row + 512; chunks cover pk_threads * pk_vpt rows. With pk_ofs the same non-zeros
+  // in batches of 12 with 16-bit byte offsets 8 d (dc_packets.h: second layout), pk_ptr still in 16-byte units
   const int4 DC_G *pk;
   const int DC_C *pk_ptr;
   const int DC_C *pk_n;
   const float DC_G *sq_dinv;         // [pk_threads * pk_vpt] sqrt(1 / P_ii), 0 for padding rows
   int pk_vpt, pk_ok;            // rows per thread of the packet kernel; 0 = tables not usable (bandwidth > 511 or N too large)
   int pk_threads;               // threads of the packet kernel the tables are padded for (512 or 768)
+  int pk_ofs;                   // pk is in the byte-offset layout of the instances that hold the direction as halves (dc_packets.h)
   int adj_coarse;               // the adjoint's fp64 fall-back adds the coarse correction over the deflation space (dc_adjoint64.h)
   const double DC_G *dsph_tri;  // discretised sphere (DC_PRIM_SPHERE_DISCRETIZED): [dsph_ntri][12] = p0, p1, p2, face normal of its mesh, creation order
   int dsph_ntri;

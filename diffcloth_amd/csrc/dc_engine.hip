@@ -273,6 +273,7 @@ static bool build_deflation_cached(dc_ctx *c, const HostSystem &H, int want, int
 // DevSystem fields both kinds of context take from the table plan: the kernel set dc_get_layout reports, and what sizes the batch
 static void set_decisions(DevSystem &S, const HostTables &plan) {
   S.win_ok = plan.win_ok; S.nwin = plan.nwin; S.pk_ok = plan.pk_ok; S.pk_vpt = plan.pk_vpt; S.pk_threads = plan.pk_threads;
+  S.pk_ofs = plan.pk_ofs;
   S.fwd_defl = plan.fwd_defl; S.adj_coarse = plan.adj_coarse; S.dense_ld = plan.dense_ld;
   S.max_radii = plan.max_radii; S.self_cap = plan.self_cap; S.self_lds = plan.self_lds;
 }
@@ -652,6 +653,8 @@ int dc_build(dc_ctx *c) {
   sw.self_lds = env_not_off("DC_SELF_LDS", true);             // 0 = global-memory layer passes
   static const bool adj_coarse = env_int("DC_ADJ_COARSE", 1) != 0;      // 0 = block preconditioner only in the adjoint's fall-back
   sw.adj_coarse = adj_coarse;
+  sw.pk_h16 = pk_h16_enabled() != 0;
+  sw.pk_ofs = env_not_off("DC_PK_OFS", true);                 // 0 = the first packet layout (10-bit column deltas) for the halves instances too
   HostTables plan;
   plan.build(H, p, sw);
   HostDeflation *HD = nullptr;
@@ -1467,6 +1470,13 @@ int dc_get_deflation(const dc_ctx *c, int *vectors, int *probe_iterations) {
   if (!c->built) return DC_ERR_STATE;
   if (vectors) *vectors = c->defl_k;
   if (probe_iterations) *probe_iterations = c->defl_probe;
+  return DC_OK;
+}
+
+int dc_get_packet_layout(const dc_ctx *c, int *byte_offsets) {
+  if (!c || !byte_offsets) return DC_ERR_INVALID;
+  if (!c->built) return DC_ERR_STATE;
+  *byte_offsets = c->S.pk_ofs;
   return DC_OK;
 }
 

@@ -9,7 +9,9 @@
 //   * off-diagonals travel as 16-byte packets {v0, v1, v2, d0 | d1 << 10 | d2 << 20}: three fp32 values and three
 //     10-bit column deltas relative to the row (biased by 512) = 5.33 B per non-zero instead of 8, one
 //     global_load_dwordx4 per three non-zeros, wave-sliced so a wave reads 1 KiB contiguous per instruction;
-//     the next row's packets are in flight while the current row is consumed;
+//     the next row's packets are in flight while the current row is consumed; the instances that hold the direction
+//     as halves read 12 values + 12 16-bit byte offsets per batch instead (6 B per non-zero, dc_packets.h), which
+//     takes one address instruction per non-zero instead of two;
 //   * the search direction p lives in LDS as a float2 (x, y) plane + a float z plane (a neighbour costs one
 //     ds_read_b64 + one ds_read_b32), the residual r and A p in registers, the iterate x in registers for the
 //     first VPT - XL rows of a thread and in the LDS left over by p for the rest: nothing of a CG iteration
@@ -32,6 +34,7 @@ bool launch_pd_step_packet(const DevSystem &S, const DevWork &W, const FwdArgs &
   if (!S.pk_ok) return false;
   if (S.defl_u && S.fwd_defl) return launch_pd_step_packet_deflated(S, W, A, B, st);
   const int h16 = pk_h16_enabled();      // (development switch DC_PK_H16, dc_env.h)
+  if (S.pk_ofs && !(h16 && S.win_ok)) return false;      // byte-offset tables are built for the instances with the direction as halves only (dc_tables.cpp)
   if (S.pk_threads == 768) {
     if (S.pk_vpt != 14) return false;
     if (h16 && S.win_ok) launch_pk_h16<768, 14, 7>(S, W, A, B, st);

@@ -17,6 +17,7 @@ static void launch_deflated(const DevSystem &S, const DevWork &W, const FwdArgs 
 bool launch_pd_step_packet_deflated(const DevSystem &S, const DevWork &W, const FwdArgs &A, int B, hipStream_t st) {
   if (!S.pk_ok || !S.defl_u || S.pk_threads != 512) return false;
   const int h16 = pk_h16_enabled();
+  if (S.pk_ofs && !(h16 && S.win_ok && S.pk_vpt == 20)) return false;      // (as in launch_pd_step_packet)
   switch (S.pk_vpt) {
     case 4: launch_deflated<4, 0>(S, W, A, B, st); break;
     case 6: launch_deflated<6, 0>(S, W, A, B, st); break;

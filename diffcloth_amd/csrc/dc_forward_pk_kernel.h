@@ -35,9 +35,11 @@ namespace dc {
 // registers. CG does not need an exact direction, only consistency: the step length is the exact line search along the direction actually
 // used, alpha = <d, r> / <d, A d>, and r, x are updated with that same d, so r stays the residual of x (fp32, as before) and the stopping
 // rule is unchanged; the rounding of d (2^-11 relative) costs a little conjugacy, nothing else. Needs the element windows (S.win_ok).
-template <int THREADS, int VPT, int XL, bool DETECT, bool DENSE, bool H16, bool DEFL>
-__global__ __launch_bounds__(THREADS) void k_pd_step_pk(const DevSystem *__restrict__ Sp, DevWork W, FwdArgs A) {
+// OFS (with H16): the packet matrix is in its byte-offset layout (dc_packets.h, S.pk_ofs) — one address instruction per non-zero of the product.
+template <int THREADS, int VPT, int XL, bool DETECT, bool DENSE, bool H16, bool DEFL, bool OFS>
+__device__ __forceinline__ void pd_step_pk(const DevSystem *__restrict__ Sp, const DevWork &W, const FwdArgs &A) {
   static_assert(!(H16 && DENSE), "the explicit-inverse solve keeps the fp32 planes");
+  static_assert(H16 || !OFS, "byte offsets address the direction's 8-byte rows");
   const DevSystem &S = *Sp;
   constexpr int NP = THREADS * VPT;
   constexpr int WAVES = THREADS / 64;
@@ -401,24 +403,21 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_pk(const DevSystem *__restr
         const int zl = wz - wv;
         auto row_of = [&](int k) -> const int4 DC_G * {
           const unsigned lo = (unsigned) __builtin_amdgcn_readlane((int) tbl_lo, k + zl), hi = (unsigned) __builtin_amdgcn_readlane((int) tbl_hi, k + zl);
-          return (const int4 DC_G *) (((unsigned long long) hi << 32) | lo) + lane;
+          return (const int4 DC_G *) (((unsigned long long) hi << 32) | lo);
         };
-        int4 nxt[PB];
+        using Batch = std::conditional_t<OFS, PkOfsBatch, PkDeltaBatch>;      // the packet matrix's layout (dc_packets.h)
+        Batch nxt;
         const int4 DC_G *row = row_of(0);
-#pragma unroll
-        for (int j = 0; j < PB; j++) nxt[j] = row[j * 64];
+        load_h_batch(nxt, row, lane, 0);
 #pragma unroll
         for (int k = 0; k < VPT; k++) {
           const int i = (wz + k * WAVES) * 64 + lane;
           const int np = __builtin_amdgcn_readlane(tbl_n, k + zl);
-          int4 cur[PB];
-#pragma unroll
-          for (int j = 0; j < PB; j++) cur[j] = nxt[j];
+          const Batch cur = nxt;
           const int4 DC_G *row_next = row;
           if (k + 1 < VPT) {
             row_next = row_of(k + 1);
-#pragma unroll
-            for (int j = 0; j < PB; j++) nxt[j] = row_next[j * 64];
+            load_h_batch(nxt, row_next, lane, 0);
           }
           unsigned rowbase = lh_addr + 8u * (unsigned) (i - 512);
           asm volatile("" : "+v"(rowbase));      // opaque: one register per row, not (row + delta) * 8 + LDS base per non-zero
@@ -426,9 +425,9 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_pk(const DevSystem *__restr
           pk_v2i own;
           consume_h_row(cur, rowbase, ax, ay, az, own);
           for (int s0 = PB; s0 < np; s0 += PB) {        // rows wider than one batch
-#pragma unroll
-            for (int j = 0; j < PB; j++) cur[j] = row[(s0 + j) * 64];
-            consume_h(cur, rowbase, ax, ay, az);
+            Batch more;
+            load_h_batch(more, row, lane, s0 / PB);
+            consume_h(more, rowbase, ax, ay, az);
           }
           row = row_next;
           ap[k][0] = ax; ap[k][1] = ay; ap[k][2] = az;
@@ -683,9 +682,27 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_pk(const DevSystem *__restr
   }   // step
 }
 
+// The instances with the direction as halves read the packet matrix by byte offsets; k_pd_step_pk_d10 is the same kernel on the first
+// layout (10-bit column deltas), which DC_PK_OFS=0 selects at dc_build.
+template <int THREADS, int VPT, int XL, bool DETECT, bool DENSE, bool H16, bool DEFL>
+__global__ __launch_bounds__(THREADS) void k_pd_step_pk(const DevSystem *__restrict__ Sp, DevWork W, FwdArgs A) {
+  pd_step_pk<THREADS, VPT, XL, DETECT, DENSE, H16, DEFL, H16>(Sp, W, A);
+}
+template <int THREADS, int VPT, int XL, bool DETECT, bool DEFL>
+__global__ __launch_bounds__(THREADS) void k_pd_step_pk_d10(const DevSystem *__restrict__ Sp, DevWork W, FwdArgs A) {
+  pd_step_pk<THREADS, VPT, XL, DETECT, false, true, DEFL, false>(Sp, W, A);
+}
+
 template <int THREADS, int VPT, int XL, bool DETECT, bool DENSE, bool H16 = false, bool DEFL = false>
 static void launch_pk_inst(const DevSystem &S, const DevWork &W, const FwdArgs &A, int B, hipStream_t st) {
   const size_t lds = pk_lds_bytes(THREADS, VPT, XL, H16, DENSE, S.dense_ld, S.win_ok, S.win_lds_bytes, A.inline_detect);
+  if constexpr (H16) {
+    if (!S.pk_ofs) {
+      (void) ensure_dynamic_lds<k_pd_step_pk_d10<THREADS, VPT, XL, DETECT, DEFL>>(lds);
+      hipLaunchKernelGGL((k_pd_step_pk_d10<THREADS, VPT, XL, DETECT, DEFL>), dim3(B), dim3(THREADS), lds, st, S.self_dev, W, A);
+      return;
+    }
+  }
   (void) ensure_dynamic_lds<k_pd_step_pk<THREADS, VPT, XL, DETECT, DENSE, H16, DEFL>>(lds);      // (refused: the launch reports it)
   hipLaunchKernelGGL((k_pd_step_pk<THREADS, VPT, XL, DETECT, DENSE, H16, DEFL>), dim3(B), dim3(THREADS), lds, st, S.self_dev, W, A);
 }

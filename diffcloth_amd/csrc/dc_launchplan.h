@@ -21,6 +21,7 @@ constexpr int kGranuleBytes = 16;      // one exchange granule {x, y, z, tag} (v
 constexpr long long kSpinLimit = 200000000ll;     // bound of every spin of the exchange: 2 s of the 100 MHz wall clock
 constexpr int kSelfCells = 4096;               // bins of the 2-D broad-phase grid of the self-contact detection
 constexpr int kSelfDetectLdsInts = 16 + (kSelfCells + 1) + kSelfCells + 1 + 2048;   // LDS ints self_detect_rollout needs
+constexpr int kPkOfsBatchInt4 = 4 * 64 + 32;   // 16-byte units of a 64-row chunk's batch (12 non-zeros per row) in the packet matrix's byte-offset layout (dc_packets.h)
 constexpr int kCoarseVectors = 16;
 constexpr int kCoarseLdsFloats = 2 * (16 * 3 * kCoarseVectors + 3 * kCoarseVectors);      // scratch of precondition64 in floats (16 = waves or parts, at most)
 // explicit inverse of small systems (dc_denselib.h): number of column chunks the product is split into so that every wave of the workgroup

@@ -83,4 +83,32 @@ bool HostPackets::build_rows(const HostSystem &H, int rows_padded) {
   return true;
 }
 
+void HostPackets::to_offsets() {
+  if (!ok || ofs) return;
+  std::vector<int> out, ptr(pk_ptr.size(), 0);
+  for (size_t ch = 0; ch < pk_ptr.size(); ch++) {
+    const int nb = pk_n[ch] / 4;
+    ptr[ch] = (int) (out.size() / 4);
+    out.resize(out.size() + (size_t) 4 * kPkOfsBatchInt4 * nb, 0);
+    for (int t = 0; t < nb; t++) {
+      int *b = &out[4 * ((size_t) ptr[ch] + (size_t) kPkOfsBatchInt4 * t)];
+      for (int l = 0; l < 64; l++) {
+        unsigned o[12];
+        for (int j = 0; j < 4; j++) {
+          const int *q = &pk[4 * ((size_t) pk_ptr[ch] + (size_t) (4 * t + j) * 64 + l)];
+          for (int k = 0; k < 3; k++) {
+            const int n = 3 * j + k;                                 // non-zero n of the batch: value dword n, offset field n
+            b[4 * (32 + 64 * (n / 4) + l) + n % 4] = q[k];
+            o[n] = 8u * (((unsigned) q[3] >> (10 * k)) & 1023u);
+          }
+        }
+        for (int w = 0; w < 4; w++) b[4 * (32 + 64 * 3 + l) + w] = (int) (o[2 * w] | o[2 * w + 1] << 16);
+        for (int w = 0; w < 2; w++) b[2 * l + w] = (int) (o[8 + 2 * w] | o[9 + 2 * w] << 16);
+      }
+    }
+  }
+  pk.swap(out); pk_ptr.swap(ptr);
+  ofs = true;
+}
+
 }  // namespace dc

@@ -3,14 +3,26 @@
 // off-diagonals packed three to a 16-byte packet {v0, v1, v2, d0 | d1 << 10 | d2 << 20} with d = column - row + 512,
 // wave-sliced: chunk c = rows 64c .. 64c+63, packet (s, lane) at pk[4 * (pk_ptr[c] + 64 s + lane)], pk_n[c] packets per
 // row (a multiple of 4). Padding packets are {0, 0, 0, 512 | 512 << 10 | 512 << 20} (value 0 on the row itself).
+//
+// Second layout (to_offsets; the kernels that hold the search direction as 8-byte rows of halves): the same non-zeros in the same order,
+// each with the BYTE offset 8 d of its column's direction entry from the entry of row - 512, as a 16-bit field — the kernel forms the
+// LDS address of a gather with one add that selects the field (dc_pklib.h: gather_o) instead of a bit-field extract and a shift-add.
+// A batch of 4 packets (12 non-zeros) becomes 18 dwords per lane, wave-sliced as one 8-byte slice of offsets {o8 | o9 << 16, o10 | o11 << 16},
+// three 16-byte slices of values {v0 .. v3}, {v4 .. v7}, {v8 .. v11} and one 16-byte slice of offsets {o0 | o1 << 16, ..., o6 | o7 << 16} (the
+// 8-byte slice first: every slice then lies within the 4095 bytes a global load's immediate offset reaches from the batch's start):
+// batch t of chunk c starts at pk[4 * (pk_ptr[c] + kPkOfsBatchInt4 * t)], the 8-byte slice at + 2 * lane, 16-byte slice j at
+// + 4 * (32 + 64 j + lane). 6 B per non-zero instead of 5.33. pk_n stays the packet count of the first layout (4 per batch), pk_ptr stays in
+// 16-byte units. Padding entries are value 0, offset 8 * 512 (the row itself).
 #pragma once
 #include <vector>
+#include "dc_launchplan.h"
 #include "dc_system.h"
 
 namespace dc {
 
 struct HostPackets {
   bool ok = false;
+  bool ofs = false;               // pk is in the second layout (byte-offset fields)
   int vpt = 0;                    // rows per thread of the kernel the tables are padded for (threads * vpt rows)
   int threads = 512;              // threads of that kernel: 512, or 768 for the largest meshes (3 waves per SIMD, dc_forward_pk.hip)
   int bandwidth = 0;              // max |column - row| of P
@@ -22,6 +34,8 @@ struct HostPackets {
   bool build(const HostSystem &H);
   // the same tables padded to `rows_padded` rows (a multiple of 64, >= N), any N; false when the bandwidth exceeds 511
   bool build_rows(const HostSystem &H, int rows_padded);
+  // rewrites pk / pk_ptr from the first layout into the second (pk_n, sq_dinv unchanged)
+  void to_offsets();
 };
 
 }  // namespace dc

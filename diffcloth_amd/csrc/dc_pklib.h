@@ -3,6 +3,7 @@
 #pragma once
 #include <type_traits>
 #include "dc_devlib.h"
+#include "dc_launchplan.h"
 
 namespace dc {
 namespace {
@@ -143,6 +144,70 @@ __device__ __forceinline__ void consume_h_row(const int4 (&e)[PB], unsigned rowb
     fma3_h(__int_as_float(e[j].y), q[j][1].x, q[j][1].y, ax, ay, az);
     fma3_h(__int_as_float(e[j].z), q[j][2].x, q[j][2].y, ax, ay, az);
   }
+  asm("v_fma_mix_f32 %0, 1.0, %1, %0 op_sel_hi:[0,1,0]" : "+v"(ax) : "v"(o.x));
+  asm("v_fma_mix_f32 %0, 1.0, %1, %0 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "+v"(ay) : "v"(o.x));
+  asm("v_fma_mix_f32 %0, 1.0, %1, %0 op_sel_hi:[0,1,0]" : "+v"(az) : "v"(o.y));
+  own = o;
+}
+// a batch of the first layout as one value, and its load by batch index (`chunk`: the chunk's first packet, wave-uniform), for the product
+// loop that is written once for both layouts (dc_forward_pk_kernel.h)
+struct PkDeltaBatch { int4 e[PB]; };
+__device__ __forceinline__ void load_h_batch(PkDeltaBatch &b, const int4 DC_G *chunk, int lane, int t) {
+  const int4 DC_G *row = chunk + lane;
+#pragma unroll
+  for (int j = 0; j < PB; j++) b.e[j] = row[(t * PB + j) * 64];
+}
+__device__ __forceinline__ void consume_h(const PkDeltaBatch &b, unsigned rowbase, float &ax, float &ay, float &az) { consume_h(b.e, rowbase, ax, ay, az); }
+__device__ __forceinline__ void consume_h_row(const PkDeltaBatch &b, unsigned rowbase, float &ax, float &ay, float &az, pk_v2i &own) { consume_h_row(b.e, rowbase, ax, ay, az, own); }
+// The same two consumers for the packet matrix's byte-offset layout (dc_packets.h): a batch is 12 values and 12 16-bit fields 8 d, two to a
+// dword, and the gather's LDS address is rowbase + field in ONE instruction, an add whose second operand selects the low or the high
+// half of the dword (SDWA) — 5 wave-instructions per non-zero instead of 6. The functions overload consume_h / consume_h_row on the batch type. Written out for the reason given at the v_bfe_u32 extracts
+// above: from `rowbase + (w & 0xffff)` / `rowbase + (w >> 16)` the compiler makes a mask or a shift and a separate add.
+// Same gathers, same products in the same order as consume_h / consume_h_row: only the way an address is obtained differs.
+struct PkOfsBatch { int4 v[3]; int4 o; pk_v2i o2; };
+// `chunk`: the chunk's first batch (wave-uniform: both slices' loads are scalar base + lane offset), t: batch
+__device__ __forceinline__ void load_h_batch(PkOfsBatch &e, const int4 DC_G *chunk, int lane, int t) {
+  const int4 DC_G *b = chunk + t * kPkOfsBatchInt4;
+  unsigned lane8 = 8u * (unsigned) lane;
+  asm("" : "+v"(lane8));      // (opaque: derived from one lane index, the 16-byte slices' 16 * lane is rebuilt from this slice's 8 * lane in 64-bit adds)
+  e.o2 = *(const pk_v2i DC_G *) ((const char DC_G *) b + lane8);      // the 8-byte slice leads the batch
+#pragma unroll
+  for (int j = 0; j < 3; j++) e.v[j] = b[32 + j * 64 + lane];
+  e.o = b[32 + 3 * 64 + lane];
+}
+__device__ __forceinline__ void gather_o(const PkOfsBatch &e, unsigned rowbase, pk_v2i (&q)[12]) {
+  const int w[6] = {e.o.x, e.o.y, e.o.z, e.o.w, e.o2.x, e.o2.y};
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    unsigned a0, a1;
+    asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0" : "=v"(a0) : "v"(rowbase), "v"(w[j]));
+    asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1" : "=v"(a1) : "v"(rowbase), "v"(w[j]));
+    q[2 * j] = *(lds_int2p) (size_t) a0;
+    q[2 * j + 1] = *(lds_int2p) (size_t) a1;
+  }
+}
+__device__ __forceinline__ void products_o(const PkOfsBatch &e, const pk_v2i (&q)[12], float &ax, float &ay, float &az) {
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    fma3_h(__int_as_float(e.v[j].x), q[4 * j].x, q[4 * j].y, ax, ay, az);
+    fma3_h(__int_as_float(e.v[j].y), q[4 * j + 1].x, q[4 * j + 1].y, ax, ay, az);
+    fma3_h(__int_as_float(e.v[j].z), q[4 * j + 2].x, q[4 * j + 2].y, ax, ay, az);
+    fma3_h(__int_as_float(e.v[j].w), q[4 * j + 3].x, q[4 * j + 3].y, ax, ay, az);
+  }
+}
+__device__ __forceinline__ void consume_h(const PkOfsBatch &e, unsigned rowbase, float &ax, float &ay, float &az) {
+  pk_v2i q[12];
+  gather_o(e, rowbase, q);
+  __builtin_amdgcn_sched_barrier(0);      // (see consume_h)
+  products_o(e, q, ax, ay, az);
+}
+__device__ __forceinline__ void consume_h_row(const PkOfsBatch &e, unsigned rowbase, float &ax, float &ay, float &az, pk_v2i &own) {
+  pk_v2i q[12];
+  gather_o(e, rowbase, q);
+  pk_v2i o = *(lds_int2p) (size_t) (rowbase + 4096u);
+  __builtin_amdgcn_sched_barrier(0);
+  ax = 0.f; ay = 0.f; az = 0.f;
+  products_o(e, q, ax, ay, az);
   asm("v_fma_mix_f32 %0, 1.0, %1, %0 op_sel_hi:[0,1,0]" : "+v"(ax) : "v"(o.x));
   asm("v_fma_mix_f32 %0, 1.0, %1, %0 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "+v"(ay) : "v"(o.x));
   asm("v_fma_mix_f32 %0, 1.0, %1, %0 op_sel_hi:[0,1,0]" : "+v"(az) : "v"(o.y));

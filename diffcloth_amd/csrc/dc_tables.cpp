@@ -69,6 +69,9 @@ void HostTables::build(const HostSystem &H, const dc_params &p, const TableSwitc
   // packet-ELL copy of the scaled matrix for dc_forward_pk.hip (dc_packets.h)
   if (pk.build(H)) {
     pk_ok = 1; pk_vpt = pk.vpt; pk_threads = pk.threads;
+    // the instances that hold the search direction as halves (dc_forward_pk.hip: 512 x 20 and 768 x 14, with the element windows) gather
+    // by byte offsets
+    if (sw.pk_ofs && sw.pk_h16 && win_ok && (pk_threads == 768 || pk_vpt == 20)) { pk.to_offsets(); pk_ofs = 1; }
   } else {
     // no packet tables (matrix bandwidth beyond the +-511 of their column deltas: the reference's 17 562-vertex dress, 647 after
     // renumbering): the scaling D^-1/2 alone, for the coarse level of the ADJOINT's preconditioner (dc_adjoint64.h), which such a mesh needs

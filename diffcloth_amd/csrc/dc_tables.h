@@ -24,6 +24,8 @@ struct TableSwitches {
   int dense_max_n = 0;      // DC_DENSE_MAX_N: largest mesh that gets the explicit inverse (0 disables)
   bool self_lds = true;     // DC_SELF_LDS=0: layered self-contact passes through global memory
   bool adj_coarse = true;   // DC_ADJ_COARSE=0: no coarse level over the deflation space in the adjoint's fall-back
+  bool pk_h16 = true;       // DC_PK_H16=0: the packet kernels' 20- and 14-rows-per-thread instances keep the fp32 direction planes
+  bool pk_ofs = true;       // DC_PK_OFS=0: the instances with the direction as halves read the packet matrix in its first layout
 };
 
 struct HostTables {
@@ -31,6 +33,7 @@ struct HostTables {
   int bandwidth = 0;                   // max |column - row| of P
   int win_ok = 0, nwin = 0;            // element windows (win)
   int pk_ok = 0, pk_vpt = 0, pk_threads = 0;   // packet matrix (pk): rows per thread and threads of its kernel, 0 when the tables are refused
+  int pk_ofs = 0;                      // pk is in the byte-offset layout (dc_packets.h): the kernel that runs holds the direction as halves
   int defl_rows = 0;                   // row padding of the deflation tables: the packet kernel's rows, or N rounded up to 64; 0 = no space wanted
   int fwd_defl = 0, adj_coarse = 0;    // set_deflation
   int dense_ld = 0;                    // explicit inverse (dense): its leading dimension, 0 = not built

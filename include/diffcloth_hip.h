@@ -346,6 +346,9 @@ int dc_get_self_friction_path(dc_ctx *ctx, int *out /*B*2*/, int reset);
  * LDS element windows usable, number of element windows, explicit-inverse solve (small meshes)}. A mesh that fails the packet /
  * window conditions runs on the global-memory fallback kernels — correct, but several times slower. */
 int dc_get_layout(const dc_ctx *ctx, int *out6);
+/* Layout of the packet matrix dc_build chose (works on a host-only context): 1 = 16-bit byte offsets (the forward kernel instances that hold
+ * the search direction as halves), 0 = 10-bit column deltas or no packet matrix. DC_PK_OFS=0 at dc_build keeps the column deltas.   */
+int dc_get_packet_layout(const dc_ctx *ctx, int *byte_offsets);
 /* Deflation space of the forward solve dc_build chose (works on a host-only context): number of vectors (0 = none) and the iteration
  * count of the probe solve that decided (Jacobi-PCG to 1e-4 on a smooth right-hand side).                                            */
 int dc_get_deflation(const dc_ctx *ctx, int *vectors, int *probe_iterations);
