@@ -59,7 +59,7 @@ EXPORTED_SYMBOLS = [
     "dc_step_forward", "dc_get_record", "dc_get_contacts", "dc_get_self_contacts", "dc_step_backward", "dc_rollout_forward",
     "dc_seed_gradient", "dc_rollout_backward", "dc_get_gradient", "dc_get_param_gradients", "dc_get_stats", "dc_sync", "dc_timer_start",
     "dc_timer_stop", "dc_kernel_times", "dc_get_cluster", "dc_set_gradient", "dc_set_fixed_point_schedule", "dc_set_force_schedule",
-    "dc_set_seed_schedule", "dc_clear_schedules", "dc_get_states", "dc_get_dxfixed", "dc_get_layout", "dc_get_packet_layout", "dc_comm_unique_id", "dc_comm_init", "dc_allreduce_sum", "dc_comm_destroy",
+    "dc_set_seed_schedule", "dc_clear_schedules", "dc_get_states", "dc_get_dxfixed", "dc_get_layout", "dc_get_packet_layout", "dc_get_bend_rows", "dc_comm_unique_id", "dc_comm_init", "dc_allreduce_sum", "dc_comm_destroy",
     "dc_get_deflation", "dc_set_record", "dc_set_trajectory_start", "dc_keep_force_gradients", "dc_get_force_gradients", "dc_use_stream", "dc_set_state_dev", "dc_get_state_dev", "dc_step_forward_dev", "dc_step_backward_dev",
     "dc_get_self_friction_path", "dc_get_adjoint_matrix", "dc_dense_phase_times",
 ]
@@ -477,6 +477,12 @@ class Engine:
         """True when dc_build laid the packet matrix out with byte offsets (dc_get_packet_layout; DC_PK_OFS=0 keeps the column deltas)"""
         k = C.c_int()
         self._chk(self.lib.dc_get_packet_layout(self.h, C.byref(k)))
+        return bool(k.value)
+
+    def bend_rows(self):
+        """True when dc_build turned the bending term into per-vertex matrix rows (dc_get_bend_rows; a mesh flat at rest, DC_BEND_ROWS=0 keeps the flaps)"""
+        k = C.c_int()
+        self._chk(self.lib.dc_get_bend_rows(self.h, C.byref(k)))
         return bool(k.value)
 
     def deflation(self):

@@ -298,6 +298,8 @@ __device__ __forceinline__ void adjoint_operator(const DevSystem &S, const AdjCt
   // (one pass over the list of their vertices); both leave y in global memory, every other vertex is staged as z itself. (Before:
   // two passes over all N vertices per operator application, 49 k of its 290 k cycles on the 10 000-vertex cloth with 500 self and
   // 400 primitive contacts; forming y_i inside the staging instead costs three dependent loads per span vertex, halo included.)
+  // (flat-rest bending as matrix rows, S.win_rows: at every call below the rows read the staged y plane — input 1, sign +, the defaults of
+  // element_windows — so a contact vertex's y is what the staging put there, from the LDS list included)
   APH_DECL
   if (C.nself == 0 && (C.mark == nullptr || S.nwin < 4)) {
     // primitive contacts only on a mesh of a few windows (the garment scenes): an operator application there is a chain of latencies, and

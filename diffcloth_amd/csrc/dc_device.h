@@ -96,7 +96,12 @@ struct DevSystem {
   const int DC_C *winc_ptr;
   const int DC_C *winc_n;
   int nwin, win_vcap, win_nrcap, win_ok;
-  int win_lds_bytes, pad2;
+  int win_lds_bytes;
+  int win_rows;                 // flat-rest bending as matrix rows (dc_windows.h): the windows have no flaps, the flap-pair packets of winc hold
+                                // {position in the span, bits(h^2 B_ij)} and the per-vertex phase sums coef (a_j - a_i) over a staged input plane
+  const int DC_G *brow_ptr;          // the same rows by vertex index, CSR without the diagonal: [N + 1]; null without rows
+  const int DC_G *brow_col;
+  const double DC_G *brow_val;       // h^2 B_ij
   // self-collision (Simulation.cpp:194-220, 225-373): collision radii, connected-pair table (share a triangle)
   const float DC_G *radii;           // [N]
   const int DC_G *conn_ptr;          // [N+1]

@@ -273,7 +273,7 @@ static bool build_deflation_cached(dc_ctx *c, const HostSystem &H, int want, int
 // DevSystem fields both kinds of context take from the table plan: the kernel set dc_get_layout reports, and what sizes the batch
 static void set_decisions(DevSystem &S, const HostTables &plan) {
   S.win_ok = plan.win_ok; S.nwin = plan.nwin; S.pk_ok = plan.pk_ok; S.pk_vpt = plan.pk_vpt; S.pk_threads = plan.pk_threads;
-  S.pk_ofs = plan.pk_ofs;
+  S.pk_ofs = plan.pk_ofs; S.win_rows = plan.bend_rows;
   S.fwd_defl = plan.fwd_defl; S.adj_coarse = plan.adj_coarse; S.dense_ld = plan.dense_ld;
   S.max_radii = plan.max_radii; S.self_cap = plan.self_cap; S.self_lds = plan.self_lds;
 }
@@ -655,6 +655,7 @@ int dc_build(dc_ctx *c) {
   sw.adj_coarse = adj_coarse;
   sw.pk_h16 = pk_h16_enabled() != 0;
   sw.pk_ofs = env_not_off("DC_PK_OFS", true);                 // 0 = the first packet layout (10-bit column deltas) for the halves instances too
+  sw.bend_rows = env_not_off("DC_BEND_ROWS", true);           // 0 = per-flap bending passes on meshes that are flat at rest too
   HostTables plan;
   plan.build(H, p, sw);
   HostDeflation *HD = nullptr;
@@ -724,6 +725,11 @@ int dc_build(dc_ctx *c) {
     if ((rc = upload_as<int>(c, &S.winc, HW.inc))) return rc;
     if ((rc = upload<int>(c, &S.winc_ptr, HW.inc_ptr))) return rc;
     if ((rc = upload<int>(c, &S.winc_n, HW.inc_n))) return rc;
+    if (HW.rows) {
+      if ((rc = upload<int>(c, &S.brow_ptr, HW.brow_ptr))) return rc;
+      if ((rc = upload<int>(c, &S.brow_col, HW.brow_col))) return rc;
+      if ((rc = upload<double>(c, &S.brow_val, HW.brow_val))) return rc;
+    }
     S.win_vcap = HW.vcap; S.win_nrcap = HW.nrcap; S.win_lds_bytes = (int) HW.lds_bytes;
   }
   if (plan.pk_ok) {
@@ -1477,6 +1483,13 @@ int dc_get_packet_layout(const dc_ctx *c, int *byte_offsets) {
   if (!c || !byte_offsets) return DC_ERR_INVALID;
   if (!c->built) return DC_ERR_STATE;
   *byte_offsets = c->S.pk_ofs;
+  return DC_OK;
+}
+
+int dc_get_bend_rows(const dc_ctx *c, int *rows) {
+  if (!c || !rows) return DC_ERR_INVALID;
+  if (!c->built) return DC_ERR_STATE;
+  *rows = c->S.win_rows;
   return DC_OK;
 }
 

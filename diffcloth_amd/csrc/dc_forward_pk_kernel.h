@@ -104,7 +104,22 @@ __device__ __forceinline__ void pd_step_pk(const DevSystem *__restrict__ Sp, con
     if (A.fv2) fext = fext + ld3(A.fv2 + off, i, N);
     f3 v0 = v + fext * (h / m);                   // (s_n - x_n) / h
     st3(vnow, i, N, v0);
-    st3(g, i, N, v0 * m);                         // M (s_n - x_n) / h
+    f3 gi = v0 * m;                               // M (s_n - x_n) / h
+    if (S.win_rows) {
+      // flat-rest bending as matrix rows (dc_windows.h): the flaps' force -h w^2 e(x_n + h v) is linear, and its x_n part,
+      // -(1 / h) sum_j (h^2 B)_ij (x_n,j - x_n,i), is constant over the step's PD iterations; the windows add the v part per iteration
+      const f3 xi = ld3(xn, i, N);
+      double bx = 0, by = 0, bz = 0;
+      const int k1 = S.brow_ptr[i + 1];
+      for (int k = S.brow_ptr[i]; k < k1; k++) {
+        const f3 xj = ld3(xn, S.brow_col[k], N);
+        const double c = S.brow_val[k];
+        bx += c * ((double) xj.x - (double) xi.x); by += c * ((double) xj.y - (double) xi.y); bz += c * ((double) xj.z - (double) xi.z);
+      }
+      const double ih = -1.0 / S.h64;
+      gi = gi + mk((float) (ih * bx), (float) (ih * by), (float) (ih * bz));
+    }
+    st3(g, i, N, gi);
     part += dot(v0, v0);
     int prim = -1;
     f3 nrm = mk(0, 0, 0);
@@ -182,7 +197,8 @@ __device__ __forceinline__ void pd_step_pk(const DevSystem *__restrict__ Sp, con
         part += dot(rhs, rhs);
       };
 #endif
-      element_windows<THREADS, kFwdOpsPrecise>(S, lp, StagePlanar{xn, N}, vnow, fwd_tri_op(h, S.h64), fwd_bend_op(h, S.h64), vert);   // fp64-strain operators (dc_winlib.h)
+      // (flat-rest bending as matrix rows, S.win_rows: the rows read the staged v plane, input 2, and enter with the sign of -h w^2 e)
+      element_windows<THREADS, kFwdOpsPrecise, 2, -1>(S, lp, StagePlanar{xn, N}, vnow, fwd_tri_op(h, S.h64), fwd_bend_op(h, S.h64), vert);   // fp64-strain operators (dc_winlib.h)
       __syncthreads();
       PH(0)
       if (nself > 0 && !A.self_full) {

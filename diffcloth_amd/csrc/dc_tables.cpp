@@ -65,7 +65,7 @@ void HostTables::build(const HostSystem &H, const dc_params &p, const TableSwitc
     }
   }
   // element windows: the local step and the adjoint's element pass run inside LDS
-  if (sw.windows && win.build(H, kWindowLdsBudget)) { win_ok = 1; nwin = win.nwin; }
+  if (sw.windows && win.build(H, kWindowLdsBudget, sw.bend_rows, p.time_step)) { win_ok = 1; nwin = win.nwin; bend_rows = win.rows ? 1 : 0; }
   // packet-ELL copy of the scaled matrix for dc_forward_pk.hip (dc_packets.h)
   if (pk.build(H)) {
     pk_ok = 1; pk_vpt = pk.vpt; pk_threads = pk.threads;

@@ -26,6 +26,7 @@ struct TableSwitches {
   bool adj_coarse = true;   // DC_ADJ_COARSE=0: no coarse level over the deflation space in the adjoint's fall-back
   bool pk_h16 = true;       // DC_PK_H16=0: the packet kernels' 20- and 14-rows-per-thread instances keep the fp32 direction planes
   bool pk_ofs = true;       // DC_PK_OFS=0: the instances with the direction as halves read the packet matrix in its first layout
+  bool bend_rows = true;    // DC_BEND_ROWS=0: a mesh whose flaps are all flat at rest keeps the per-flap passes too (dc_windows.h: rows)
 };
 
 struct HostTables {
@@ -33,6 +34,7 @@ struct HostTables {
   int bandwidth = 0;                   // max |column - row| of P
   int win_ok = 0, nwin = 0;            // element windows (win)
   int pk_ok = 0, pk_vpt = 0, pk_threads = 0;   // packet matrix (pk): rows per thread and threads of its kernel, 0 when the tables are refused
+  int bend_rows = 0;                   // the windows of the one-workgroup kernels carry the bending term as matrix rows, no flaps (win.rows)
   int pk_ofs = 0;                      // pk is in the byte-offset layout (dc_packets.h): the kernel that runs holds the direction as halves
   int defl_rows = 0;                   // row padding of the deflation tables: the packet kernel's rows, or N rounded up to 64; 0 = no space wanted
   int fwd_defl = 0, adj_coarse = 0;    // set_deflation

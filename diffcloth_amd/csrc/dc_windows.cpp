@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 
 namespace dc {
 
@@ -9,7 +10,7 @@ namespace {
 
 inline int fbits(float v) { int b; std::memcpy(&b, &v, sizeof(int)); return b; }
 
-struct Plan { int nwin = 0, vcap = 0, nrcap = 0; };
+struct Plan { int nwin = 0, vcap = 0, nrcap = 0, nrcap_rows = 0; };      // nrcap_rows: without the flaps' result slots (HostWindows::rows)
 
 // window w of `own` vertices: which elements touch it and which vertex span they cover
 struct WinScan {
@@ -95,13 +96,36 @@ Plan plan_for(const HostSystem &H, int own, const std::vector<int> &emin, const 
     // + the zero vector the padding entries of the incidence rows point at + one dump slot per lane for the masked elements of the
     // last round (dc_winlib.h: their stores are redirected, not skipped)
     p.nrcap = std::max(p.nrcap, 2 * nt + nb + 1 + kWinDumpSlots);
+    p.nrcap_rows = std::max(p.nrcap_rows, 2 * nt + 1 + kWinDumpSlots);
   }
   return p;
 }
 
+// every flap in the linear branch of its operator: exactly the device's test (dc_winlib.h: `n > 1e-6f` on the fp32 rest norm)
+bool all_flaps_flat(const HostSystem &H) {
+  if (H.E <= 0) return false;
+  for (int e = 0; e < H.E; e++)
+    if (!((float) H.bend_n[e] <= 1e-6f)) return false;
+  return true;
+}
+
+// B_ij = sum over the flaps of vertex i of w^2 (corner weight of i) (edge weight of j), fp64, off-diagonals only
+std::vector<std::map<int, double>> bend_matrix_rows(const HostSystem &H) {
+  std::vector<std::map<int, double>> B(H.N);
+  for (int e = 0; e < H.E; e++) {
+    const int *q = &H.bend_v[4 * e];
+    const double *w = &H.bend_w[4 * (size_t) e];
+    const double ew[4] = {-(w[1] + w[2] + w[3]), w[1], w[2], w[3]};
+    for (int c = 0; c < 4; c++)
+      for (int d = 0; d < 4; d++)
+        if (q[d] != q[c]) B[q[c]][q[d]] += H.bend_w2[e] * w[c] * ew[d];
+  }
+  return B;
+}
+
 }  // namespace
 
-bool HostWindows::build(const HostSystem &H, size_t lds_budget) {
+bool HostWindows::build(const HostSystem &H, size_t lds_budget, bool want_rows, double h) {
   *this = HostWindows();
   const int N = H.N, T = H.T, E = H.E;
   if (N <= 0 || T <= 0) return false;
@@ -134,10 +158,10 @@ bool HostWindows::build(const HostSystem &H, size_t lds_budget) {
     Plan p = plan_for(H, rounded, emin, emax);
     best = p; best_own = rounded;
   }
-  return build_own(H, best_own);
+  return build_own(H, best_own, want_rows, h);
 }
 
-bool HostWindows::build_own(const HostSystem &H, int own_size) {
+bool HostWindows::build_own(const HostSystem &H, int own_size, bool want_rows, double h) {
   *this = HostWindows();
   const int N = H.N, T = H.T, E = H.E;
   if (N <= 0 || T <= 0 || own_size <= 0 || own_size % 64 != 0) return false;
@@ -154,7 +178,17 @@ bool HostWindows::build_own(const HostSystem &H, int own_size) {
   const Plan best = plan_for(H, own_size, emin, emax);
   if (best.vcap > 65535 || best.nrcap > 32767) return false;      // positions travel as 15 bits + sign
   const int best_own = own_size;
-  own = best_own; nwin = best.nwin; vcap = best.vcap; nrcap = best.nrcap;
+  rows = want_rows && all_flaps_flat(H);
+  own = best_own; nwin = best.nwin; vcap = best.vcap; nrcap = rows ? best.nrcap_rows : best.nrcap;
+  std::vector<std::map<int, double>> B;
+  if (rows) {
+    B = bend_matrix_rows(H);
+    brow_ptr.assign(N + 1, 0);
+    for (int v = 0; v < N; v++) {
+      for (const auto &jc : B[v]) { brow_col.push_back(jc.first); brow_val.push_back(h * h * jc.second); }
+      brow_ptr[v + 1] = (int) brow_col.size();
+    }
+  }
   lds_bytes = sizeof(float) * ((size_t) 6 * vcap + (size_t) 3 * nrcap);
 
   const int nchunks = (N + 63) / 64;
@@ -169,6 +203,7 @@ bool HostWindows::build_own(const HostSystem &H, int own_size) {
       order_by_first_use(H, v0, v1, false, s.tris);
       order_by_first_use(H, v0, v1, true, s.bends);
     }
+    if (rows) s.bends.clear();      // (the span keeps the flaps' vertices: the rows read them)
     const int ntri = (int) s.tris.size(), nbend = (int) s.bends.size();
     const int tri_off = (int) (tri_rec.size() / 4), bend_off = (int) (bend_rec.size() / 4);
     const int d[8] = {v0, v1, s.lo, s.hi - s.lo, tri_off, ntri, bend_off, nbend};
@@ -199,7 +234,7 @@ bool HostWindows::build_own(const HostSystem &H, int own_size) {
     const int zero_slot = 2 * ntri + nbend;
     for (int ch = v0 / 64; ch < (v1 + 63) / 64; ch++) {
       std::vector<std::vector<int>> codes(64);
-      std::vector<std::vector<std::pair<int, float>>> rows(64);
+      std::vector<std::vector<std::pair<int, float>>> vrows(64);
       int wt = 0, wb = 0;
       for (int l = 0; l < 64; l++) {
         const int v = 64 * ch + l;
@@ -212,13 +247,15 @@ bool HostWindows::build_own(const HostSystem &H, int own_size) {
             if (corner == 1) codes[l].push_back(p0 << 1);
             else if (corner == 2) codes[l].push_back(p1 << 1);
             else { codes[l].push_back((p0 << 1) | 1); codes[l].push_back((p1 << 1) | 1); }
-          } else {
+          } else if (!rows) {
             const int corner = (idx - 3 * T) / E, e = (idx - 3 * T) % E;
-            rows[l].push_back({2 * ntri + bend_local[e], (float) H.bend_w[4 * e + corner]});
+            vrows[l].push_back({2 * ntri + bend_local[e], (float) H.bend_w[4 * e + corner]});
           }
         }
+        if (rows)
+          for (int k = brow_ptr[v]; k < brow_ptr[v + 1]; k++) vrows[l].push_back({brow_col[k] - s.lo, (float) brow_val[k]});
         wt = std::max(wt, (int) codes[l].size());
-        wb = std::max(wb, (int) rows[l].size());
+        wb = std::max(wb, (int) vrows[l].size());
       }
       const int nt4 = std::max(1, (wt + 7) / 8);             // packets of 8 triangle entries
       const int nb4 = std::max(2, ((wb + 1) / 2 + 1) / 2 * 2);   // packets of 2 flap pairs, an even number of them
@@ -231,13 +268,15 @@ bool HostWindows::build_own(const HostSystem &H, int own_size) {
           const size_t o = base + 4 * ((size_t) (k / 8) * 64 + l) + (k % 8) / 2;
           inc[o] |= (k % 2) ? (code << 16) : code;
         }
-        for (size_t k = 0; k < rows[l].size(); k++) {
+        for (size_t k = 0; k < vrows[l].size(); k++) {
           const size_t o = base + 4 * ((size_t) (nt4 + k / 2) * 64 + l) + 2 * (k % 2);
-          inc[o] = rows[l][k].first; inc[o + 1] = fbits(rows[l][k].second);
+          inc[o] = vrows[l][k].first; inc[o + 1] = fbits(vrows[l][k].second);
         }
-        for (size_t k = rows[l].size(); k < (size_t) 2 * nb4; k++) {      // padding pairs: the zero vector, weight 0
+        // padding pairs: the zero vector, weight 0 (rows: the vertex's own position in the span — lanes past the last vertex: the window's last)
+        const int pad = rows ? std::min(64 * ch + l, v1 - 1) - s.lo : zero_slot;
+        for (size_t k = vrows[l].size(); k < (size_t) 2 * nb4; k++) {
           const size_t o = base + 4 * ((size_t) (nt4 + k / 2) * 64 + l) + 2 * (k % 2);
-          inc[o] = zero_slot; inc[o + 1] = 0;
+          inc[o] = pad; inc[o + 1] = 0;
         }
       }
     }

@@ -42,10 +42,23 @@ struct HostWindows {
   // inc[inc_ptr[c] + 64 s + lane], s < nt4; then nb4 packets {q0, bits(w0), q1, bits(w1)} of flap pairs, s - nt4 < nb4
   std::vector<int> inc;
   std::vector<int> inc_ptr, inc_n;
+  // Flat-rest bending as matrix rows (`want_rows`, time step `h`). A flap whose rest norm is zero is in the linear branch of its operator for good
+  // (the device's test `n > 1e-6f` never holds): forward -h w^2 e, adjoint h^2 w^2 sum_c w_c (y_c - y_0), both with e = sum_c w_c (a_c - a_0) a fixed
+  // linear map of the staged vector. Summed over a vertex's corners that is one sparse row, sum_j B_ij (a_j - a_i) with
+  // B = sum_flaps w^2 (corner weight) (x) (edge weights), edge weight of corner 0 = -(w1 + w2 + w3); B depends on the rest mesh, k_bend and h only.
+  // When EVERY flap of the mesh passes (float) bend_n <= 1e-6f — all or nothing — the windows carry no flaps (nbend = 0, no bend_rec / bend_w /
+  // bend_lo, no flap result slots in nrcap) and the flap-pair packets of `inc` hold the row instead: {pos, bits(coef), pos, bits(coef)} with
+  // pos = j - lo, the neighbour's position in the window's SPAN (an input plane, not a result vector), coef = fl32(h^2 B_ij), B accumulated in
+  // fp64; entries ordered by column; no diagonal entry (the device sums coef (a_j - a_i); the rows of B sum to zero); padding entries point at
+  // the vertex's own position with coefficient 0. The window size is chosen as without rows (the sizing pass counts the flaps), and the spans
+  // still cover every flap vertex. Any other mesh gets the per-flap tables, byte for byte.
+  bool rows = false;
+  std::vector<int> brow_ptr, brow_col;     // the same rows by global vertex index, CSR: [N + 1], columns ascending, no diagonal
+  std::vector<double> brow_val;            // h^2 B_ij in fp64 (the forward kernel's per-step set-up: the x_n part of the bending force)
 
-  bool build(const HostSystem &H, size_t lds_budget);
+  bool build(const HostSystem &H, size_t lds_budget, bool want_rows = false, double h = 0.0);
   // the same tables for a given window size (`own_size` owned vertices per window, a multiple of 64); no LDS check
-  bool build_own(const HostSystem &H, int own_size);
+  bool build_own(const HostSystem &H, int own_size, bool want_rows = false, double h = 0.0);
 };
 
 }  // namespace dc

@@ -117,12 +117,25 @@ template <class O> __device__ __forceinline__ VertNoA<O> vert_noa(O o) { return 
 template <class V, class = void> struct vert_ignores_a : std::false_type {};
 template <class V> struct vert_ignores_a<V, std::enable_if_t<V::kIgnoresInput1>> : std::true_type {};
 
+// Flat-rest bending as matrix rows (dc_windows.h: HostWindows::rows; S.win_rows, wave-uniform): the windows have no flaps, and the flap-pair
+// packets of the per-vertex phase hold {position in the span, h^2 B_ij}. The gather then reads a staged INPUT plane instead of the result planes
+// and each term is coef (a_j - a_i), a_i from the vertex's own slot. The caller states at compile time which plane the rows read and the sign
+// the row sum enters `sum` with: ROW_PLANE = 1, ROW_SIGN = +1 (the adjoint: h^2 w^2 sum_c w_c (y_c - y_0) of y, input 1) or ROW_PLANE = 2,
+// ROW_SIGN = -1 (the forward local step: -h w^2 e, of which the window supplies the part linear in v, input 2; the x_n part is constant over a
+// step and sits in g, dc_forward_pk_kernel.h). Since the per-vertex phase then reads an input plane, the barrier NOA operators skip is taken.
+// A table set without the member (the split kernels' DevCluster, which keep their flaps) compiles the row code out.
+template <class TB, class = void> struct tb_has_rows : std::false_type {};
+template <class TB> struct tb_has_rows<TB, std::void_t<decltype(std::declval<const TB &>().win_rows)>> : std::true_type {};
+template <class TB> __device__ __forceinline__ bool table_rows(const TB &S) {
+  if constexpr (tb_has_rows<TB>::value) return S.win_rows != 0; else return false;
+}
+
 template <int EB, bool PRECISE>
 struct WinTriRecs { int4 r[EB]; float4 D[EB]; float4 Dl[PRECISE ? EB : 1]; };
 template <int EB, bool PRECISE>
 struct WinBendRecs { int4 r[EB]; float4 w[EB]; float4 wl[PRECISE ? EB : 1]; };
 
-template <int THREADS, bool PRECISE = false, class TB, class Stage1, class In2, class TriOp, class BendOp, class VertOp>
+template <int THREADS, bool PRECISE = false, int ROW_PLANE = 1, int ROW_SIGN = 1, class TB, class Stage1, class In2, class TriOp, class BendOp, class VertOp>
 __device__ __forceinline__ void element_windows_t(const TB &S, int w0, int w1, float *lds, Stage1 stage1,
                                                   In2 in2, TriOp tri_op, BendOp bend_op, VertOp vert_op) {
   const int tid = threadIdx.x, lane = tid & 63;
@@ -130,6 +143,9 @@ __device__ __forceinline__ void element_windows_t(const TB &S, int w0, int w1, f
   constexpr int MB = kWinMaxBatch;
   constexpr int VPB = 6;
   constexpr bool PAIR = THREADS < 1024;
+  const bool rows = table_rows(S);
+  const float2 *rxy = ROW_PLANE == 2 ? L.a2xy : L.a1xy;
+  const float *rz = ROW_PLANE == 2 ? L.a2z : L.a1z;
   for (int w = w0; w < w1; w++) {
     const int4 d0 = S.win[2 * w], d1 = S.win[2 * w + 1];
     const int v0 = d0.x, v1 = d0.y, lo = d0.z, vs = d0.w, toff = d1.x, nt = d1.y, boff = d1.z, nb = d1.w;
@@ -155,7 +171,7 @@ __device__ __forceinline__ void element_windows_t(const TB &S, int w0, int w1, f
     WinBendRecs<MB, PRECISE> bcur;
     const int dump = 2 * nt + nb + 1 + lane;      // kWinDumpSlots result slots behind the zero vector (dc_windows.cpp: nrcap)
     constexpr bool NOA = vert_ignores_a<VertOp>::value;
-    if (!NOA || w == w0) __syncthreads();      // (NOA: the previous window's per-vertex phase reads the result planes only; the staging below writes the input planes)
+    if (!NOA || rows || w == w0) __syncthreads();      // (NOA: the previous window's per-vertex phase reads the result planes only — unless it gathers matrix rows; the staging below writes the input planes)
     // SVR span vertices per thread and round (clamped index, no divergence): their global loads overlap. A span is ~1.3 windows wide:
     // three vertices per thread stage it in ONE round of the 512-thread kernels (two rounds = two exposed memory round trips per window
     // before: 5.2 k of a window's 29 k cycles in the forward step), two in one round of the 1024-thread kernels.
@@ -329,15 +345,22 @@ __device__ __forceinline__ void element_windows_t(const TB &S, int w0, int w1, f
         sx = fmaf(c, q.x, sx); sy = fmaf(c, q.y, sy); sz = fmaf(c, z, sz);
       }
     };
-    auto gather = [&](const int4 (&e)[VPB], int s0, int np, float &sx, float &sy, float &sz) {
+    // (rows, wave-uniform: the entries are positions in the staged input plane and the terms coef (a_j - a_i), a_i from the vertex's own slot `own`;
+    //  without rows a_i = 0 and the sign +1: q - 0 and c * 1 are exact, the sums are the ones they have always been)
+    const float2 *gxy = rows ? rxy : L.erxy;
+    const float *gz = rows ? rz : L.erz;
+    const float gsign = rows ? (float) ROW_SIGN : 1.f;
+    auto gather = [&](const int4 (&e)[VPB], int s0, int np, int own, float &sx, float &sy, float &sz) {
+      f3 ai = mk(0, 0, 0);
+      if (rows) ai = ldw(rxy, rz, own);
 #pragma unroll
       for (int j = 0; j < VPB; j++) {
-        const float on = (s0 + j < np) ? 1.f : 0.f;
-        const float2 qa = L.erxy[e[j].x], qb = L.erxy[e[j].z];
-        const float za = L.erz[e[j].x], zb = L.erz[e[j].z];
+        const float on = (s0 + j < np) ? gsign : 0.f;
+        const float2 qa = gxy[e[j].x], qb = gxy[e[j].z];
+        const float za = gz[e[j].x], zb = gz[e[j].z];
         const float ca = __int_as_float(e[j].y) * on, cb = __int_as_float(e[j].w) * on;
-        sx = fmaf(ca, qa.x, sx); sy = fmaf(ca, qa.y, sy); sz = fmaf(ca, za, sz);
-        sx = fmaf(cb, qb.x, sx); sy = fmaf(cb, qb.y, sy); sz = fmaf(cb, zb, sz);
+        sx = fmaf(ca, qa.x - ai.x, sx); sy = fmaf(ca, qa.y - ai.y, sy); sz = fmaf(ca, za - ai.z, sz);
+        sx = fmaf(cb, qb.x - ai.x, sx); sy = fmaf(cb, qb.y - ai.y, sy); sz = fmaf(cb, zb - ai.z, sz);
       }
     };
     for (int i = v0 + tid; i < v1; i += (PAIR ? 2 : 1) * THREADS) {
@@ -368,8 +391,8 @@ __device__ __forceinline__ void element_windows_t(const TB &S, int w0, int w1, f
             gather_tri(ta1, nta > 1, ax, ay, az);
             gather_tri(tb1, ntb > 1, bx, by, bz);
           }
-          gather(ea, 0, nba, ax, ay, az);
-          gather(eb, 0, nbb, bx, by, bz);
+          gather(ea, 0, nba, i - lo, ax, ay, az);
+          gather(eb, 0, nbb, (vb ? ib : i) - lo, bx, by, bz);
         }
         for (int s0 = 2; s0 < max(nta, ntb); s0++) {      // vertices of more than 16 triangle entries
           const int4 ta = rowa[min(s0, nta - 1) * 64], tb = rowb[min(s0, ntb - 1) * 64];
@@ -380,8 +403,8 @@ __device__ __forceinline__ void element_windows_t(const TB &S, int w0, int w1, f
           int4 ea[VPB], eb[VPB];
 #pragma unroll
           for (int j = 0; j < VPB; j++) { ea[j] = frowa[min(s0 + j, nba - 1) * 64]; eb[j] = frowb[min(s0 + j, nbb - 1) * 64]; }
-          gather(ea, s0, nba, ax, ay, az);
-          gather(eb, s0, nbb, bx, by, bz);
+          gather(ea, s0, nba, i - lo, ax, ay, az);
+          gather(eb, s0, nbb, (vb ? ib : i) - lo, bx, by, bz);
         }
         if constexpr (vert_has_pre<VertOp>::value) {
           vert_op(i, mk(ax, ay, az), ldw(L.a1xy, L.a1z, i - lo), prea);
@@ -399,14 +422,14 @@ __device__ __forceinline__ void element_windows_t(const TB &S, int w0, int w1, f
           for (int j = 0; j < VPB; j++) ea[j] = frowa[min(j, nba - 1) * 64];
           gather_tri(ta, true, ax, ay, az);
           if (nta > 1) gather_tri(ta1, true, ax, ay, az);
-          gather(ea, 0, nba, ax, ay, az);
+          gather(ea, 0, nba, i - lo, ax, ay, az);
         }
         for (int s0 = 2; s0 < nta; s0++) gather_tri(rowa[s0 * 64], true, ax, ay, az);
         for (int s0 = VPB; s0 < nba; s0 += VPB) {
           int4 ea[VPB];
 #pragma unroll
           for (int j = 0; j < VPB; j++) ea[j] = frowa[min(s0 + j, nba - 1) * 64];
-          gather(ea, s0, nba, ax, ay, az);
+          gather(ea, s0, nba, i - lo, ax, ay, az);
         }
         if constexpr (vert_has_pre<VertOp>::value) vert_op(i, mk(ax, ay, az), ldw(L.a1xy, L.a1z, i - lo), prea);
         else vert_op(i, mk(ax, ay, az), ldw(L.a1xy, L.a1z, i - lo));
@@ -416,10 +439,10 @@ __device__ __forceinline__ void element_windows_t(const TB &S, int w0, int w1, f
   }
 }
 
-template <int THREADS, bool PRECISE = false, class Stage1, class TriOp, class BendOp, class VertOp>
+template <int THREADS, bool PRECISE = false, int ROW_PLANE = 1, int ROW_SIGN = 1, class Stage1, class TriOp, class BendOp, class VertOp>
 __device__ __forceinline__ void element_windows(const DevSystem &S, float *lds, Stage1 stage1,
                                                 const float *__restrict__ in2, TriOp tri_op, BendOp bend_op, VertOp vert_op) {
-  element_windows_t<THREADS, PRECISE>(S, 0, S.nwin, lds, stage1, In2Plain{in2, S.N}, tri_op, bend_op, vert_op);
+  element_windows_t<THREADS, PRECISE, ROW_PLANE, ROW_SIGN>(S, 0, S.nwin, lds, stage1, In2Plain{in2, S.N}, tri_op, bend_op, vert_op);
 }
 
 // ---- forward local step: a = x_n, b = v (current iterate); x = x_n + h v, edges formed as differences first ----

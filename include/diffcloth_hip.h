@@ -349,6 +349,10 @@ int dc_get_layout(const dc_ctx *ctx, int *out6);
 /* Layout of the packet matrix dc_build chose (works on a host-only context): 1 = 16-bit byte offsets (the forward kernel instances that hold
  * the search direction as halves), 0 = 10-bit column deltas or no packet matrix. DC_PK_OFS=0 at dc_build keeps the column deltas.   */
 int dc_get_packet_layout(const dc_ctx *ctx, int *byte_offsets);
+/* Whether dc_build turned the bending term of the one-workgroup kernels into per-vertex matrix rows (works on a host-only context): 1 = every
+ * flap of the mesh is flat at rest (fp32 rest norm <= 1e-6) and the element windows carry no flaps, 0 = per-flap passes (any curved flap, no
+ * element windows, or DC_BEND_ROWS=0 at dc_build). The split kernels keep their flaps either way.                                     */
+int dc_get_bend_rows(const dc_ctx *ctx, int *rows);
 /* Deflation space of the forward solve dc_build chose (works on a host-only context): number of vectors (0 = none) and the iteration
  * count of the probe solve that decided (Jacobi-PCG to 1e-4 on a smooth right-hand side).                                            */
 int dc_get_deflation(const dc_ctx *ctx, int *vectors, int *probe_iterations);
