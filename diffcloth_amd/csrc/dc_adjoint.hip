@@ -18,7 +18,6 @@
 #define DC_KERNEL_TU
 #include <cstdlib>
 #include "dc_devlib.h"
-#include "dc_env.h"
 #include "dc_winlib.h"
 #include "dc_denselib.h"
 #include "dc_adjprecond.h"
@@ -968,16 +967,6 @@ __global__ __launch_bounds__(THREADS) void k_adjoint_step(const DevSystem *__res
   }   // step
 }
 
-static int pick_threads_bwd(int N) {
-  static const int forced = env_int("DC_BWD_THREADS", 0);     // development switch
-  if (forced == 256 || forced == 512 || forced == 1024) return forced;
-  // 16 waves per rollout at every mesh size: the Krylov iteration is a chain of barrier-separated phases with global-memory
-  // round trips, and with one workgroup per CU (256 rollouts) only the waves of that workgroup can hide them — measured
-  // 1.3 - 1.7 x over 256 / 512 threads from N = 579 to N = 3634 (tools/bench_configs.py), even with idle lanes at N < 1024
-  (void) N;
-  return 1024;
-}
-
 // Launch of a windowed instance with `base` bytes of dynamic LDS (adj_lds_bytes) plus the contact vertices' y list in what that leaves of the
 // CU's LDS (adj_ylist). The device's limit and the instance's static LDS are queried once per (device, instance), not assumed; when the device
 // refuses the larger request the launch goes without the list (ycap = 0) instead of failing without a diagnosis.
@@ -1009,8 +998,8 @@ static void launch_adj_lds(const DevSystem &S, const DevWork &W, const BwdArgs &
   hipLaunchKernelGGL(Kernel, dim3(B), dim3(THREADS), lds, st, S.self_dev, W, Ay);
 }
 template <int THREADS, bool DENSE, bool BLK>
-static void launch_adj_b(const DevSystem &S, const DevWork &W, const BwdArgs &A, int B, hipStream_t st) {
-  if (!S.win_ok) { hipLaunchKernelGGL((k_adjoint_step<THREADS, false, false, false>), dim3(B), dim3(THREADS), 0, st, S.self_dev, W, A); return; }
+static void launch_adj_b(const DevSystem &S, const DevWork &W, const BwdArgs &A, const AdjChoice &ch, int B, hipStream_t st) {
+  if (!ch.win) { hipLaunchKernelGGL((k_adjoint_step<THREADS, false, false, false>), dim3(B), dim3(THREADS), 0, st, S.self_dev, W, A); return; }
   launch_adj_lds<k_adjoint_step<THREADS, true, DENSE, BLK>, THREADS>(S, W, A, B, st, adj_lds_bytes(THREADS, true, S.win_lds_bytes, DENSE, S.dense_ld, false));
 }
 // the instances with the coarse level of the preconditioner (meshes the engine built a deflation space for, direct solve, block preconditioner):
@@ -1020,25 +1009,31 @@ static void launch_adj_coarse(const DevSystem &S, const DevWork &W, const BwdArg
   launch_adj_lds<k_adjoint_step<THREADS, true, false, true, true>, THREADS>(S, W, A, B, st, adj_lds_bytes(THREADS, true, S.win_lds_bytes, false, S.dense_ld, true));
 }
 template <int THREADS, bool DENSE>
-static void launch_adj(const DevSystem &S, const DevWork &W, const BwdArgs &A, int B, hipStream_t st) {
-  // the block preconditioner belongs to the direct solve (mode 1); the reference's iteration (mode 0) uses P^-1 as the reference does
-  if (A.block_pre && A.mode == 1 && !DENSE) launch_adj_b<THREADS, DENSE, true>(S, W, A, B, st);
-  else launch_adj_b<THREADS, DENSE, false>(S, W, A, B, st);
+static void launch_adj(const DevSystem &S, const DevWork &W, const BwdArgs &A, const AdjChoice &ch, int B, hipStream_t st) {
+  if (ch.blk) launch_adj_b<THREADS, DENSE, true>(S, W, A, ch, B, st);
+  else launch_adj_b<THREADS, DENSE, false>(S, W, A, ch, B, st);
 }
 
-void launch_adjoint_step(const DevSystem &S, const DevWork &W, const BwdArgs &A, int B, hipStream_t st) {
 #ifdef DC_ADJ_ONLY_BENCH      // development builds: only the instances of the 10 000-vertex headline (compile time)
-  launch_adj_b<1024, false, false>(S, W, A, B, st);
+constexpr bool adj_shape_compiled(const AdjShape &s) { return s.threads == 1024 && !s.dense && !s.coarse; }
 #else
-  // small meshes, reference iteration (mode 0): the inner solve with P is one product with the explicit inverse (dc_dense.h)
-  if (S.dense_inv && S.win_ok && A.mode == 0 && pick_threads_bwd(S.N) == 1024) { launch_adj<1024, true>(S, W, A, B, st); return; }
-  if (S.adj_coarse && S.defl_u && S.win_ok && S.win_lds_bytes / 4 >= kCoarseLdsFloats && A.block_pre && A.mode == 1 && pick_threads_bwd(S.N) == 1024) { launch_adj_coarse<1024>(S, W, A, B, st); return; }
-  switch (pick_threads_bwd(S.N)) {
-    case 256: launch_adj<256, false>(S, W, A, B, st); break;
-    case 512: launch_adj<512, false>(S, W, A, B, st); break;
-    default: launch_adj<1024, false>(S, W, A, B, st); break;
-  }
+constexpr bool adj_shape_compiled(const AdjShape &) { return true; }
 #endif
+
+// The one instance the adjoint choice names (dc_kernelplan.h: adjoint_choice, made per enqueue from the step's arguments): one walk of
+// kAdjShapes at compile time instantiates every shape's kernels.
+hipError_t launch_adjoint_step(const DevSystem &S, const DevWork &W, const BwdArgs &A, const AdjChoice &ch, int B, hipStream_t st) {
+  const bool hit = for_first_index<kAdjShapeCount>([&](auto i) {
+    constexpr AdjShape s = kAdjShapes[i];
+    if constexpr (!adj_shape_compiled(s)) return false;
+    else {
+      if (ch.threads != s.threads || ch.dense != s.dense || ch.coarse != s.coarse) return false;
+      if constexpr (s.coarse) launch_adj_coarse<s.threads>(S, W, A, B, st);
+      else launch_adj<s.threads, s.dense>(S, W, A, ch, B, st);
+      return true;
+    }
+  });
+  return hit ? hipPeekAtLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace dc

@@ -609,10 +609,10 @@ static hipError_t launch_adj_cl_inst(const DevSystem &S, const DevCluster &CL, c
   hipLaunchKernelGGL((k_adjoint_step_cl<THREADS, BLK, COARSE>), dim3((nb + 7) / 8 * 8 * CL.K), dim3(THREADS), l.bytes, st, S.self_dev, CL.self_dev, W, A, b0, nb, l.hc_off, l.tail_off);
   return hipGetLastError();
 }
-hipError_t launch_adjoint_step_cluster(const DevSystem &S, const DevCluster &CL, const DevWork &W, const BwdArgs &A, int b0, int nb, hipStream_t st) {
+hipError_t launch_adjoint_step_cluster(const DevSystem &S, const DevCluster &CL, const DevWork &W, const BwdArgs &A, const ClAdjChoice &ch, int b0, int nb, hipStream_t st) {
   // (with the coarse level: the fall-back is an instance of its own, dc_adjoint.hip launch_adj_coarse)
-  if (A.block_pre && S.adj_coarse && S.defl_u) return launch_adj_cl_inst<true, true>(S, CL, W, A, b0, nb, st);
-  return A.block_pre ? launch_adj_cl_inst<true, false>(S, CL, W, A, b0, nb, st) : launch_adj_cl_inst<false, false>(S, CL, W, A, b0, nb, st);
+  if (ch.coarse) return launch_adj_cl_inst<true, true>(S, CL, W, A, b0, nb, st);
+  return ch.blk ? launch_adj_cl_inst<true, false>(S, CL, W, A, b0, nb, st) : launch_adj_cl_inst<false, false>(S, CL, W, A, b0, nb, st);
 }
 
 }  // namespace dc

@@ -10,7 +10,6 @@ bool ClusterPlan::fit(const HostSystem &H, int bandwidth, int Kc, bool forced) {
   const int N = H.N;
   if (Kc < 2 || bandwidth <= 0 || bandwidth > 511) return false;
   const int HBc = std::max(64, round64(bandwidth));
-  static const int allowed[] = {1, 2, 3, 4, 6, 8, 12};
   HostWindows HW;
   int Rf = 0, w_f = 0, vpt = 0;
   for (int w = 1; w <= 8 && Rf == 0; w++) {
@@ -21,8 +20,7 @@ bool ClusterPlan::fit(const HostSystem &H, int bandwidth, int Kc, bool forced) {
     if (Rc < 256 && !forced) break;                      // parts of fewer rows than half a workgroup: nothing left to save (the 1426-vertex
                                                          // T-shirt, one rollout: 21.9 / 19.0 / 18.4 / 18.2 ms per fwd+bwd step at K = 1 / 4 / 6 / 8
                                                          // once its parts share an XCD, tools/bench_tshirt_k.py)
-    int v = 0;
-    for (int a : allowed) if (a * 512 >= Rc) { v = a; break; }
+    const int v = cl_rows_for(Rc);                       // (dc_kernelplan.h: the instances of the split kernels)
     if (v == 0) continue;                                // more rows per part than the kernel holds in registers: more windows do not help
     if (!HW.build_own(H, own_w)) continue;
     const int win_floats = (int) (HW.lds_bytes / 4);

@@ -38,6 +38,8 @@ struct dc_ctx {
   const int *d_user_of = nullptr;   // device copy of user_of (null = identity)
 
   dc::DevSystem S;
+  dc::PlanFacts facts;              // the table plan's decisions and the forward step's kernel instance chosen from them (dc_kernelplan.h),
+  dc::FwdChoice fwd;                // set by dc_build with the other decisions (host-only contexts too)
   std::vector<void *> table_allocs;
 
   int B = 0, tape = 0;

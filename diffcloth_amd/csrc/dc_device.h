@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/diffcloth_hip.h"
+#include "dc_kernelplan.h"
 
 namespace dc {
 
@@ -226,13 +227,14 @@ struct BwdArgs {
   float *ys;                    // y = (I + dr_df)^T u* of the step, kept per tape slot (dc_keep_force_gradients; steps by slot_state) or nullptr
 };
 
-void launch_pd_step(const DevSystem &S, const DevWork &W, const FwdArgs &A, int B, hipStream_t st);
-// LDS/register-resident variant (dc_forward_res.hip); returns false when N is too large for it.
-bool pd_step_fusable(const DevSystem &S);   // launch_pd_step would take the packet kernel, which honours FwdArgs::nsteps
-bool launch_pd_step_packet(const DevSystem &S, const DevWork &W, const FwdArgs &A, int B, hipStream_t st);
-bool launch_pd_step_resident(const DevSystem &S, const DevWork &W, const FwdArgs &A, int B, hipStream_t st, int variant);
+// The step launchers take the choice of dc_kernelplan.h and launch the one instance it names. They return hipErrorInvalidValue, without
+// launching, when this build has no such instance; else the runtime's last error, peeked and not cleared (the engine clears it: launched()).
+hipError_t launch_pd_step(const DevSystem &S, const DevWork &W, const FwdArgs &A, const FwdChoice &ch, int B, hipStream_t st);
+hipError_t launch_pd_step_packet(const DevSystem &S, const DevWork &W, const FwdArgs &A, const FwdChoice &ch, int B, hipStream_t st);
+hipError_t launch_pd_step_packet_deflated(const DevSystem &S, const DevWork &W, const FwdArgs &A, const FwdChoice &ch, int B, hipStream_t st);
+hipError_t launch_pd_step_resident(const DevSystem &S, const DevWork &W, const FwdArgs &A, const FwdChoice &ch, int B, hipStream_t st);
 void launch_self_detect(const DevSystem &S, const DevWork &W, const FwdArgs &A, int B, hipStream_t st);
-void launch_adjoint_step(const DevSystem &S, const DevWork &W, const BwdArgs &A, int B, hipStream_t st);
+hipError_t launch_adjoint_step(const DevSystem &S, const DevWork &W, const BwdArgs &A, const AdjChoice &ch, int B, hipStream_t st);
 void launch_f64i_to_f32p(const double *src, float *dst, int B, int n, const int *user_of, hipStream_t st);
 void launch_f32p_to_f64i(const float *src, double *dst, int B, int n, const int *user_of, hipStream_t st);
 void launch_f64i_to_f64p(const double *src, double *dst, int B, int n, const int *user_of, hipStream_t st);

@@ -18,8 +18,8 @@
 using namespace dc;
 
 namespace dc {
-hipError_t launch_pd_step_cluster(const DevSystem &S, const DevCluster &CL, const DevWork &W, const FwdArgs &A, int b0, int nb, hipStream_t st);
-hipError_t launch_adjoint_step_cluster(const DevSystem &S, const DevCluster &CL, const DevWork &W, const BwdArgs &A, int b0, int nb, hipStream_t st);
+hipError_t launch_pd_step_cluster(const DevSystem &S, const DevCluster &CL, const DevWork &W, const FwdArgs &A, const ClFwdChoice &ch, int b0, int nb, hipStream_t st);
+hipError_t launch_adjoint_step_cluster(const DevSystem &S, const DevCluster &CL, const DevWork &W, const BwdArgs &A, const ClAdjChoice &ch, int b0, int nb, hipStream_t st);
 }
 
 static_assert(rec::kMetaStride == kMetaStride && rec::kMaxLayers == kMaxLayers, "dc_record.h restates dc_device.h's record sizes");
@@ -270,8 +270,12 @@ static bool build_deflation_cached(dc_ctx *c, const HostSystem &H, int want, int
   return c->defl_cache_built;
 }
 
-// DevSystem fields both kinds of context take from the table plan: the kernel set dc_get_layout reports, and what sizes the batch
-static void set_decisions(DevSystem &S, const HostTables &plan) {
+// What both kinds of context take from the table plan: the DevSystem fields of the kernel set dc_get_layout reports and of what sizes the
+// batch, and the forward step's kernel instance (dc_kernelplan.h; after set_deflation)
+static void set_decisions(dc_ctx *c, const HostTables &plan) {
+  DevSystem &S = c->S;
+  c->facts = plan.facts(c->host.N);
+  c->fwd = forward_choice(c->facts, kernel_switches());
   S.win_ok = plan.win_ok; S.nwin = plan.nwin; S.pk_ok = plan.pk_ok; S.pk_vpt = plan.pk_vpt; S.pk_threads = plan.pk_threads;
   S.pk_ofs = plan.pk_ofs; S.win_rows = plan.bend_rows;
   S.fwd_defl = plan.fwd_defl; S.adj_coarse = plan.adj_coarse; S.dense_ld = plan.dense_ld;
@@ -380,24 +384,47 @@ int enqueue_dense_adjoint(dc_ctx *c, const BwdArgs &A) {
   return DC_OK;
 }
 
+// Outcome of a step launcher that was handed a kernel choice (dc_kernelplan.h). The launchers return hipErrorInvalidValue without launching
+// when the choice names no instance of this build (development builds compile a subset), else the runtime's error, peeked: it is cleared
+// here, which also tells the two apart. Never followed by another kernel family. The message is formatted on failure only.
+static int launched(dc_ctx *c, hipError_t e, const char *step, int threads, int rows) {
+  const hipError_t runtime = hipGetLastError();
+  if (e == hipSuccess) return DC_OK;
+  const std::string shape = std::string(step) + " (" + std::to_string(threads) + " threads x " + std::to_string(rows) + " rows, N " + std::to_string(c->facts.N) + ")";
+  if (e == hipErrorInvalidValue && runtime == hipSuccess) return fail(c, DC_ERR_HIP, shape + ": this build has no such kernel instance");
+  return fail(c, DC_ERR_HIP, shape + ": " + hipGetErrorString(e));
+}
+
 int enqueue_pd_step(dc_ctx *c, const FwdArgs &A) {
   {   // a forward step overwrites records: a record handed in from outside for one of them (dc_set_record) is gone
     const long first = (long) ((A.x_out - c->X) / (long) slot_elems(c));
     if (c->inj_slot >= first && c->inj_slot < first + A.nsteps) c->inj_slot = -1;
   }
-  if (!use_cluster_fwd(c)) { launch_pd_step(c->S, c->W, A, c->B, c->stream); HIPCHK(c, hipGetLastError()); return DC_OK; }
+  if (!use_cluster_fwd(c)) {
+    const FwdChoice &ch = c->fwd;
+    return launched(c, launch_pd_step(c->S, c->W, A, ch, c->B, c->stream), ch.family == kFwdPacketDeflated ? "forward step, deflated packet kernel" :
+                    ch.family == kFwdPacket ? (ch.h16 ? "forward step, packet kernel with halves" : "forward step, packet kernel") :
+                    ch.family == kFwdResident ? "forward step, resident kernel" : ch.family == kFwdGlobal ? "forward step, global-memory kernel" :
+                    "forward step, no kernel family", ch.threads, ch.vpt);
+  }
+  const ClFwdChoice ch = cl_forward_choice(c->facts, c->cl.D.pk_vpt, kernel_switches());
   for (int b0 = 0; b0 < c->B; b0 += c->cl.nb) {
     HIPCHK(c, hipMemsetAsync(c->cl.D.xch, 0, c->cl.xch_bytes, c->stream));
-    HIPCHK(c, launch_pd_step_cluster(c->S, c->cl.D, c->W, A, b0, std::min(c->cl.nb, c->B - b0), c->stream));
+    HIPCHK(c, launch_pd_step_cluster(c->S, c->cl.D, c->W, A, ch, b0, std::min(c->cl.nb, c->B - b0), c->stream));
   }
   return DC_OK;
 }
 int enqueue_adjoint_step(dc_ctx *c, const BwdArgs &A) {
   if (c->params.adjoint_mode == 2) return enqueue_dense_adjoint(c, A);
-  if (!use_cluster_bwd(c)) { launch_adjoint_step(c->S, c->W, A, c->B, c->stream); HIPCHK(c, hipGetLastError()); return DC_OK; }
+  if (!use_cluster_bwd(c)) {
+    const AdjChoice ch = adjoint_choice(c->facts, A.mode, A.block_pre != 0, kernel_switches().bwd_threads);
+    return launched(c, launch_adjoint_step(c->S, c->W, A, ch, c->B, c->stream), ch.dense ? "adjoint step, explicit inverse" : ch.coarse ? "adjoint step, coarse level" :
+                    ch.blk ? "adjoint step, block preconditioner" : "adjoint step", ch.threads, 0);
+  }
+  const ClAdjChoice ch = cl_adjoint_choice(c->facts, A.block_pre != 0);
   for (int b0 = 0; b0 < c->B; b0 += c->cl.nb) {
     HIPCHK(c, hipMemsetAsync(c->cl.D.xch, 0, c->cl.xch_bytes, c->stream));
-    HIPCHK(c, launch_adjoint_step_cluster(c->S, c->cl.D, c->W, A, b0, std::min(c->cl.nb, c->B - b0), c->stream));
+    HIPCHK(c, launch_adjoint_step_cluster(c->S, c->cl.D, c->W, A, ch, b0, std::min(c->cl.nb, c->B - b0), c->stream));
   }
   return DC_OK;
 }
@@ -415,7 +442,7 @@ bool fuse_steps_enabled() {
 // scheduled targets. Returns the number of step-kernel launches per chunk of rollouts in *launches.
 int enqueue_forward_steps(dc_ctx *c, int slot, int nsteps, bool carry_targets, int *launches) {
   const bool self_on = c->S.contact_enabled && c->S.self_enabled, has_xf = c->S.Af > 0;
-  const bool fused = fuse_steps_enabled() && nsteps > 1 && (use_cluster_fwd(c) || pd_step_fusable(c->S));
+  const bool fused = fuse_steps_enabled() && nsteps > 1 && (use_cluster_fwd(c) || c->fwd.fusable);
   const size_t xf_bytes = sizeof(float) * xf_elems(c);
   int rc;
   FwdArgs FA = fwd_args(c, slot);          // fused: points x_fixed / fu / fv_scale at the first step's schedule entries
@@ -653,7 +680,8 @@ int dc_build(dc_ctx *c) {
   sw.self_lds = env_not_off("DC_SELF_LDS", true);             // 0 = global-memory layer passes
   static const bool adj_coarse = env_int("DC_ADJ_COARSE", 1) != 0;      // 0 = block preconditioner only in the adjoint's fall-back
   sw.adj_coarse = adj_coarse;
-  sw.pk_h16 = pk_h16_enabled() != 0;
+  sw.pk_h16 = kernel_switches().pk_h16;                       // (read once per process with the other switches that select kernel instances)
+  sw.pk_threads = env_int("DC_PK_THREADS", 0);                // 512 / 768 = threads of the packet kernel for meshes of 9 217 ... 10 240 vertices
   sw.pk_ofs = env_not_off("DC_PK_OFS", true);                 // 0 = the first packet layout (10-bit column deltas) for the halves instances too
   sw.bend_rows = env_not_off("DC_BEND_ROWS", true);           // 0 = per-flap bending passes on meshes that are flat at rest too
   HostTables plan;
@@ -666,7 +694,7 @@ int dc_build(dc_ctx *c) {
   DevSystem &S = c->S;
   if (c->host_only) {       // which kernel set this system would get (dc_get_layout): the same plan, nothing uploaded
     std::memset(&S, 0, sizeof(S));
-    set_decisions(S, plan);
+    set_decisions(c, plan);
     c->built = true;
     return DC_OK;
   }
@@ -675,7 +703,7 @@ int dc_build(dc_ctx *c) {
   free_cluster(c);
   free_pool(c->table_allocs);
   std::memset(&S, 0, sizeof(S));
-  set_decisions(S, plan);
+  set_decisions(c, plan);
   S.N = H.N; S.T = H.T; S.E = H.E; S.Af = (int) H.att_vertex.size(); S.NC = 3 * H.T + 4 * H.E;
   c->d_user_of = nullptr;
   int rc;

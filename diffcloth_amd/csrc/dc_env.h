@@ -3,6 +3,7 @@
 // enables; both give dflt when the variable is not set. env_int: atoi of the value.
 #pragma once
 #include <cstdlib>
+#include "dc_kernelplan.h"
 
 namespace dc {
 
@@ -11,10 +12,18 @@ inline bool env_on(const char *name, bool dflt) { const char *e = getenv(name); 
 inline bool env_not_off(const char *name, bool dflt) { const char *e = getenv(name); return e ? e[0] != '0' : dflt; }
 inline int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
 
-// DC_PK_H16 (read once per process): 0 = the fp32 direction planes in the packet kernels' 20-rows-per-thread instances
-inline int pk_h16_enabled() {
-  static const int h16 = env_int("DC_PK_H16", 1);
-  return h16;
+// The switches that select kernel instances (dc_kernelplan.h: KernelSwitches), read once per process at the first dc_build: DC_FWD_VARIANT,
+// DC_PK_H16, DC_BWD_THREADS, DC_SXCG
+inline const KernelSwitches &kernel_switches() {
+  static const KernelSwitches sw = [] {
+    KernelSwitches s;
+    if (env_set("DC_FWD_VARIANT")) s.fwd_variant = getenv("DC_FWD_VARIANT")[0] == 'g' ? kFwdVariantGlobal : env_int("DC_FWD_VARIANT", kFwdVariantDefault);
+    s.pk_h16 = env_int("DC_PK_H16", 1) != 0;
+    s.bwd_threads = env_int("DC_BWD_THREADS", 0);
+    s.sxcg = env_not_off("DC_SXCG", true);
+    return s;
+  }();
+  return sw;
 }
 
 }  // namespace dc

@@ -11,10 +11,8 @@
 //   P dv   = f + r(f) - M v_now ,  v_new = v_now + dv             (== v_new = P^-1 (b~ + r), :1267)
 // so the constraint residual p - A x is evaluated per element in fp32 without cancellation against P x_n,
 // and the global solve is a PCG for the *correction*, warm-started for free.
-#include <cstdlib>
 #define DC_KERNEL_TU
 #include "dc_devlib.h"
-#include "dc_env.h"
 #include "dc_winlib.h"
 
 namespace dc {
@@ -181,26 +179,23 @@ __global__ __launch_bounds__(THREADS) void k_pd_step(const DevSystem *__restrict
   }
 }
 
-static int pick_threads_fwd(int N) { return N <= 1536 ? 256 : (N <= 6144 ? 512 : 1024); }
-
-// DC_FWD_VARIANT (read once, development switch): "global" forces this file's global-memory kernel (any N);
-// "0" / "1" force the ELL resident kernel (dc_forward_res.hip) in one of its two thread shapes. Default: the
-// packet resident kernel (dc_forward_pk.hip) when its tables exist, else ELL resident, else global.
-static int fwd_variant() {
-  static const int v = !env_set("DC_FWD_VARIANT") ? -2 : (getenv("DC_FWD_VARIANT")[0] == 'g' ? -1 : env_int("DC_FWD_VARIANT", -2));
-  return v;
-}
-
-bool pd_step_fusable(const DevSystem &S) { return fwd_variant() == -2 && S.pk_ok && S.pk_vpt > 0; }
-
-void launch_pd_step(const DevSystem &S, const DevWork &W, const FwdArgs &A, int B, hipStream_t st) {
-  const int variant = fwd_variant();
-  if (variant == -2 && launch_pd_step_packet(S, W, A, B, st)) return;
-  if (variant != -1 && launch_pd_step_resident(S, W, A, B, st, variant == 1 ? 1 : 0)) return;
-  switch (pick_threads_fwd(S.N)) {
-    case 256: hipLaunchKernelGGL(k_pd_step<256>, dim3(B), dim3(256), 0, st, S.self_dev, W, A); break;
-    case 512: hipLaunchKernelGGL(k_pd_step<512>, dim3(B), dim3(512), 0, st, S.self_dev, W, A); break;
-    default: hipLaunchKernelGGL(k_pd_step<1024>, dim3(B), dim3(1024), 0, st, S.self_dev, W, A); break;
+// The one instance the forward choice names (dc_kernelplan.h: forward_choice — the packet resident kernel when its tables exist, else ELL
+// resident, else this file's global-memory kernel, any N). No family is tried after another: a choice without an instance is an error.
+hipError_t launch_pd_step(const DevSystem &S, const DevWork &W, const FwdArgs &A, const FwdChoice &ch, int B, hipStream_t st) {
+  switch (ch.family) {
+    case kFwdPacket: return launch_pd_step_packet(S, W, A, ch, B, st);
+    case kFwdPacketDeflated: return launch_pd_step_packet_deflated(S, W, A, ch, B, st);
+    case kFwdResident: return launch_pd_step_resident(S, W, A, ch, B, st);
+    case kFwdGlobal: {
+      const bool hit = for_first_index<kGlobalCount>([&](auto i) {
+        constexpr int THREADS = kGlobalLadder[i].threads;
+        if (ch.threads != THREADS) return false;
+        hipLaunchKernelGGL(k_pd_step<THREADS>, dim3(B), dim3(THREADS), 0, st, S.self_dev, W, A);
+        return true;
+      });
+      return hit ? hipPeekAtLastError() : hipErrorInvalidValue;
+    }
+    default: return hipErrorInvalidValue;
   }
 }
 

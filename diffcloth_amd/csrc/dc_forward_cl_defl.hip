@@ -6,14 +6,9 @@
 
 namespace dc {
 
-hipError_t launch_pd_step_cluster_deflated(const DevSystem &S, const DevCluster &CL, const DevWork &W, const FwdArgs &A, int b0, int nb, hipStream_t st) {
+hipError_t launch_pd_step_cluster_deflated(const DevSystem &S, const DevCluster &CL, const DevWork &W, const FwdArgs &A, const ClFwdChoice &ch, int b0, int nb, hipStream_t st) {
   if (!S.defl_u) return hipErrorInvalidValue;
-#define DC_CL_CASE(V) case V: return A.inline_detect ? launch_cl_inst<V, true, false, true>(S, CL, W, A, b0, nb, st) : launch_cl_inst<V, false, false, true>(S, CL, W, A, b0, nb, st);
-  switch (CL.pk_vpt) {
-    DC_CL_CASE(1) DC_CL_CASE(2) DC_CL_CASE(3) DC_CL_CASE(4) DC_CL_CASE(6) DC_CL_CASE(8) DC_CL_CASE(12)
-    default: return hipErrorInvalidValue;
-  }
-#undef DC_CL_CASE
+  return launch_cl_choice<true>(S, CL, W, A, ch, b0, nb, st);
 }
 
 }  // namespace dc

@@ -778,4 +778,20 @@ static hipError_t launch_cl_inst(const DevSystem &S, const DevCluster &CL, const
   return hipGetLastError();
 }
 
+// Launches the instance a split forward choice names (dc_kernelplan.h: cl_forward_choice): one walk of kClRows at compile time instantiates,
+// per rows-per-thread value, the plain instances (single- / two-exchange CG) or, with DEFL, the deflated ones (dc_forward_cl_defl.hip).
+template <bool DEFL>
+static hipError_t launch_cl_choice(const DevSystem &S, const DevCluster &CL, const DevWork &W, const FwdArgs &A, const ClFwdChoice &ch, int b0, int nb, hipStream_t st) {
+  hipError_t e = hipErrorInvalidValue;
+  for_first_index<kClRowsCount>([&](auto i) {
+    constexpr int V = kClRows[i];
+    if (ch.vpt != V) return false;
+    if constexpr (DEFL) e = A.inline_detect ? launch_cl_inst<V, true, false, true>(S, CL, W, A, b0, nb, st) : launch_cl_inst<V, false, false, true>(S, CL, W, A, b0, nb, st);
+    else if (ch.sx) e = A.inline_detect ? launch_cl_inst<V, true, true>(S, CL, W, A, b0, nb, st) : launch_cl_inst<V, false, true>(S, CL, W, A, b0, nb, st);
+    else e = A.inline_detect ? launch_cl_inst<V, true, false>(S, CL, W, A, b0, nb, st) : launch_cl_inst<V, false, false>(S, CL, W, A, b0, nb, st);
+    return true;
+  });
+  return e;
+}
+
 }  // namespace dc

@@ -23,48 +23,13 @@
 // this PCG on the correction system (see dc_forward.hip header).
 #define DC_KERNEL_TU
 #include "dc_forward_pk_kernel.h"
-#include "dc_env.h"
 
 namespace dc {
 
-bool launch_pd_step_packet_deflated(const DevSystem &S, const DevWork &W, const FwdArgs &A, int B, hipStream_t st);      // dc_forward_pk_defl.hip
-
-// 512 (or 768) threads own VPT = pk_vpt rows each (the packet tables are built for exactly that padding, dc_engine.hip).
-bool launch_pd_step_packet(const DevSystem &S, const DevWork &W, const FwdArgs &A, int B, hipStream_t st) {
-  if (!S.pk_ok) return false;
-  if (S.defl_u && S.fwd_defl) return launch_pd_step_packet_deflated(S, W, A, B, st);
-  const int h16 = pk_h16_enabled();      // (development switch DC_PK_H16, dc_env.h)
-  if (S.pk_ofs && !(h16 && S.win_ok)) return false;      // byte-offset tables are built for the instances with the direction as halves only (dc_tables.cpp)
-  if (S.pk_threads == 768) {
-    if (S.pk_vpt != 14) return false;
-    if (h16 && S.win_ok) launch_pk_h16<768, 14, 7>(S, W, A, B, st);
-    else launch_pk<768, 14, 3>(S, W, A, B, st);
-    return true;
-  }
-#ifdef DC_PK_ONLY20      // development builds: only the 10 000-vertex variant (compile time)
-  if (S.pk_vpt != 20) return false;
-  if (h16 && S.win_ok) launch_pk_h16<512, 20, 12>(S, W, A, B, st);
-  else launch_pk<512, 20, 6>(S, W, A, B, st);
-  return true;
-#else
-  switch (S.pk_vpt) {
-    case 1: launch_pk<512, 1, 0>(S, W, A, B, st); break;
-    case 2: launch_pk<512, 2, 0>(S, W, A, B, st); break;
-    case 3: launch_pk<512, 3, 0>(S, W, A, B, st); break;
-    case 4: launch_pk<512, 4, 0>(S, W, A, B, st); break;
-    case 6: launch_pk<512, 6, 0>(S, W, A, B, st); break;
-    case 8: launch_pk<512, 8, 0>(S, W, A, B, st); break;
-    case 10: launch_pk<512, 10, 0>(S, W, A, B, st); break;
-    case 12: launch_pk<512, 12, 0>(S, W, A, B, st); break;
-    case 16: launch_pk<512, 16, 2>(S, W, A, B, st); break;
-    case 20:
-      if (h16 && S.win_ok) launch_pk_h16<512, 20, 12>(S, W, A, B, st);
-      else launch_pk<512, 20, 6>(S, W, A, B, st);
-      break;
-    default: return false;
-  }
-  return true;
-#endif
+// 512 (or 768) threads own VPT = pk_vpt rows each: the packet tables are padded for exactly the shape the table plan picked from kPkShapes
+// (dc_packets.cpp, dc_kernelplan.h), and the choice names that shape's instance.
+hipError_t launch_pd_step_packet(const DevSystem &S, const DevWork &W, const FwdArgs &A, const FwdChoice &ch, int B, hipStream_t st) {
+  return launch_pk_choice<false>(S, W, A, ch, B, st);
 }
 
 }  // namespace dc

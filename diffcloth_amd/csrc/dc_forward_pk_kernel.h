@@ -723,23 +723,42 @@ static void launch_pk_inst(const DevSystem &S, const DevWork &W, const FwdArgs &
   hipLaunchKernelGGL((k_pd_step_pk<THREADS, VPT, XL, DETECT, DENSE, H16, DEFL>), dim3(B), dim3(THREADS), lds, st, S.self_dev, W, A);
 }
 
-template <int THREADS, int VPT, int XL>
-static void launch_pk(const DevSystem &S, const DevWork &W, const FwdArgs &A, int B, hipStream_t st) {
-  if constexpr (VPT <= 3) {     // small meshes: the explicit-inverse solve when the engine built it (dc_dense.h)
-    if (S.dense_inv) {
-      if (A.inline_detect) launch_pk_inst<THREADS, VPT, XL, true, true>(S, W, A, B, st);
-      else launch_pk_inst<THREADS, VPT, XL, false, true>(S, W, A, B, st);
-      return;
-    }
-  }
-  if (A.inline_detect) launch_pk_inst<THREADS, VPT, XL, true, false>(S, W, A, B, st);
-  else launch_pk_inst<THREADS, VPT, XL, false, false>(S, W, A, B, st);
+template <int THREADS, int VPT, int XL, bool DENSE, bool H16, bool DEFL>
+static void launch_pk_detect(const DevSystem &S, const DevWork &W, const FwdArgs &A, int B, hipStream_t st) {
+  if (A.inline_detect) launch_pk_inst<THREADS, VPT, XL, true, DENSE, H16, DEFL>(S, W, A, B, st);
+  else launch_pk_inst<THREADS, VPT, XL, false, DENSE, H16, DEFL>(S, W, A, B, st);
 }
-// the half-precision-direction variant (needs the element windows): XL = rows of the iterate in the LDS the 8-byte direction rows free
-template <int THREADS, int VPT, int XL>
-static void launch_pk_h16(const DevSystem &S, const DevWork &W, const FwdArgs &A, int B, hipStream_t st) {
-  if (A.inline_detect) launch_pk_inst<THREADS, VPT, XL, true, false, true>(S, W, A, B, st);
-  else launch_pk_inst<THREADS, VPT, XL, false, false, true>(S, W, A, B, st);
+
+#ifdef DC_PK_ONLY20      // development builds: only the plain instances of the 10 000-vertex shapes (compile time)
+constexpr bool pk_shape_compiled(const PkShape &s, bool defl) { return defl || s.vpt == 20 || s.threads == 768; }
+#else
+constexpr bool pk_shape_compiled(const PkShape &, bool) { return true; }
+#endif
+
+// Launches the instance a forward choice of the packet families names (dc_kernelplan.h: forward_choice): one walk of kPkShapes at compile
+// time instantiates, per shape, the halves instance (XL = xl_h16; needs the element windows), the explicit-inverse instance (small meshes,
+// when the engine built the inverse: dc_dense.h) and the plain one — those the shape has. DEFL: the deflated instances
+// (dc_forward_pk_defl.hip). hipErrorInvalidValue: the choice names no instance of this build.
+template <bool DEFL>
+static hipError_t launch_pk_choice(const DevSystem &S, const DevWork &W, const FwdArgs &A, const FwdChoice &ch, int B, hipStream_t st) {
+  const bool hit = for_first_index<kPkShapeCount>([&](auto i) {
+    constexpr PkShape s = kPkShapes[i];
+    if constexpr ((DEFL && !s.defl) || !pk_shape_compiled(s, DEFL)) return false;
+    else {
+      if (ch.threads != s.threads || ch.vpt != s.vpt) return false;
+      if (ch.h16) {      // (halves or the inverse asked of a shape without such an instance: no instance, not the plain one)
+        if constexpr (s.xl_h16 >= 0) { launch_pk_detect<s.threads, s.vpt, s.xl_h16, false, true, DEFL>(S, W, A, B, st); return true; }
+        else return false;
+      }
+      if (ch.dense) {
+        if constexpr (s.dense && !DEFL) { launch_pk_detect<s.threads, s.vpt, s.xl, true, false, DEFL>(S, W, A, B, st); return true; }
+        else return false;
+      }
+      launch_pk_detect<s.threads, s.vpt, s.xl, false, false, DEFL>(S, W, A, B, st);
+      return true;
+    }
+  });
+  return hit ? hipPeekAtLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace dc

@@ -274,21 +274,17 @@ static void launch_res(const DevSystem &S, const DevWork &W, const FwdArgs &A, i
   hipLaunchKernelGGL((k_pd_step_res<THREADS, VPT>), dim3(B), dim3(THREADS), lds, st, S.self_dev, W, A);
 }
 
-// Picks (threads, vertices per thread) so that THREADS * VPT >= N with as many waves as the register budget allows.
-bool launch_pd_step_resident(const DevSystem &S, const DevWork &W, const FwdArgs &A, int B, hipStream_t st, int variant) {
-  const int N = S.N;
-  if (N <= 256) launch_res<256, 1>(S, W, A, B, st);
-  else if (N <= 512) launch_res<256, 2>(S, W, A, B, st);
-  else if (N <= 1024) launch_res<256, 4>(S, W, A, B, st);
-  else if (N <= 1536) launch_res<256, 6>(S, W, A, B, st);
-  else if (N <= 2048) launch_res<512, 4>(S, W, A, B, st);
-  else if (N <= 4096) launch_res<512, 8>(S, W, A, B, st);
-  else if (N <= 6144) launch_res<512, 12>(S, W, A, B, st);
-  else if (N <= 8192) launch_res<1024, 8>(S, W, A, B, st);
-  else if (N <= 10240) { if (variant == 1) launch_res<512, 20>(S, W, A, B, st); else launch_res<1024, 10>(S, W, A, B, st); }
-  else if (N <= 12288) { if (variant == 1) launch_res<512, 24>(S, W, A, B, st); else launch_res<1024, 12>(S, W, A, B, st); }
-  else return false;
-  return true;
+// One walk of the ladder (dc_kernelplan.h: kResLadder) at compile time instantiates both thread shapes of every rung; the choice names one.
+hipError_t launch_pd_step_resident(const DevSystem &S, const DevWork &W, const FwdArgs &A, const FwdChoice &ch, int B, hipStream_t st) {
+  const bool hit = for_first_index<kResCount>([&](auto i) {
+    constexpr ResShape s = kResLadder[i];
+    if constexpr (s.alt_threads != s.threads || s.alt_vpt != s.vpt)
+      if (ch.threads == s.alt_threads && ch.vpt == s.alt_vpt) { launch_res<s.alt_threads, s.alt_vpt>(S, W, A, B, st); return true; }
+    if (ch.threads != s.threads || ch.vpt != s.vpt) return false;
+    launch_res<s.threads, s.vpt>(S, W, A, B, st);
+    return true;
+  });
+  return hit ? hipPeekAtLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace dc

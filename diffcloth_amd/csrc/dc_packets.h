@@ -15,7 +15,7 @@
 // 16-byte units. Padding entries are value 0, offset 8 * 512 (the row itself).
 #pragma once
 #include <vector>
-#include "dc_launchplan.h"
+#include "dc_kernelplan.h"
 #include "dc_system.h"
 
 namespace dc {
@@ -25,13 +25,14 @@ struct HostPackets {
   bool ofs = false;               // pk is in the second layout (byte-offset fields)
   int vpt = 0;                    // rows per thread of the kernel the tables are padded for (threads * vpt rows)
   int threads = 512;              // threads of that kernel: 512, or 768 for the largest meshes (3 waves per SIMD, dc_forward_pk.hip)
+  int shape = -1;                 // that kernel's entry of kPkShapes (dc_kernelplan.h); -1 = padded by build_rows for another kernel
   int bandwidth = 0;              // max |column - row| of P
   std::vector<int> pk;            // 4 ints per packet
   std::vector<int> pk_ptr, pk_n;  // per 64-row chunk
   std::vector<float> sq_dinv;     // [512 * vpt] sqrt(1 / P_ii), 0 for padding rows
 
-  // false when the tables cannot be used: N > 10 240 rows or bandwidth > 511
-  bool build(const HostSystem &H);
+  // false when the tables cannot be used: N > 10 240 rows or bandwidth > 511. want_threads: the value of DC_PK_THREADS, 0 = the default
+  bool build(const HostSystem &H, int want_threads = 0);
   // the same tables padded to `rows_padded` rows (a multiple of 64, >= N), any N; false when the bandwidth exceeds 511
   bool build_rows(const HostSystem &H, int rows_padded);
   // rewrites pk / pk_ptr from the first layout into the second (pk_n, sq_dinv unchanged)

@@ -67,11 +67,11 @@ void HostTables::build(const HostSystem &H, const dc_params &p, const TableSwitc
   // element windows: the local step and the adjoint's element pass run inside LDS
   if (sw.windows && win.build(H, kWindowLdsBudget, sw.bend_rows, p.time_step)) { win_ok = 1; nwin = win.nwin; bend_rows = win.rows ? 1 : 0; }
   // packet-ELL copy of the scaled matrix for dc_forward_pk.hip (dc_packets.h)
-  if (pk.build(H)) {
+  if (pk.build(H, sw.pk_threads)) {
     pk_ok = 1; pk_vpt = pk.vpt; pk_threads = pk.threads;
-    // the instances that hold the search direction as halves (dc_forward_pk.hip: 512 x 20 and 768 x 14, with the element windows) gather
-    // by byte offsets
-    if (sw.pk_ofs && sw.pk_h16 && win_ok && (pk_threads == 768 || pk_vpt == 20)) { pk.to_offsets(); pk_ofs = 1; }
+    // the instances that hold the search direction as halves (the shapes of kPkShapes that have one, with the element windows) gather by
+    // byte offsets
+    if (sw.pk_ofs && sw.pk_h16 && win_ok && kPkShapes[pk.shape].xl_h16 >= 0) { pk.to_offsets(); pk_ofs = 1; }
   } else {
     // no packet tables (matrix bandwidth beyond the +-511 of their column deltas: the reference's 17 562-vertex dress, 647 after
     // renumbering): the scaling D^-1/2 alone, for the coarse level of the ADJOINT's preconditioner (dc_adjoint64.h), which such a mesh needs
@@ -85,11 +85,21 @@ void HostTables::build(const HostSystem &H, const dc_params &p, const TableSwitc
 }
 
 void HostTables::set_deflation(bool built, const TableSwitches &sw) {
-  // (the deflated FORWARD kernels exist for 512 threads x >= 4 rows: meshes of more than 1536 vertices, dc_forward_pk_defl.hip; smaller meshes
+  // (the deflated FORWARD kernels exist for the shapes kPkShapes marks: meshes of more than 1536 vertices, dc_forward_pk_defl.hip; smaller meshes
   //  solve their forward step with the explicit inverse and use the space for the adjoint's coarse level only; a mesh without packet tables
   //  runs the global-memory kernel, which projects too — dc_devlib.h: deflate_global)
-  fwd_defl = (built && ((pk_ok && pk_threads == 512 && pk_vpt >= 4) || !pk_ok)) ? 1 : 0;
+  fwd_defl = (built && (!pk_ok || kPkShapes[pk.shape].defl)) ? 1 : 0;
+  defl_built = built;
   adj_coarse = (built && sw.adj_coarse) ? 1 : 0;
+}
+
+PlanFacts HostTables::facts(int N) const {
+  PlanFacts f;
+  f.N = N;
+  f.pk_ok = pk_ok != 0; f.pk_threads = pk_threads; f.pk_vpt = pk_vpt; f.win_ok = win_ok != 0; f.pk_ofs = pk_ofs != 0;
+  f.fwd_defl = fwd_defl != 0; f.adj_coarse = adj_coarse != 0; f.defl_space = defl_built; f.dense_inv = dense_ld != 0;
+  f.win_lds_bytes = win_ok ? (int) win.lds_bytes : 0;
+  return f;
 }
 
 }  // namespace dc

@@ -26,6 +26,7 @@ struct TableSwitches {
   bool adj_coarse = true;   // DC_ADJ_COARSE=0: no coarse level over the deflation space in the adjoint's fall-back
   bool pk_h16 = true;       // DC_PK_H16=0: the packet kernels' 20- and 14-rows-per-thread instances keep the fp32 direction planes
   bool pk_ofs = true;       // DC_PK_OFS=0: the instances with the direction as halves read the packet matrix in its first layout
+  int pk_threads = 0;       // DC_PK_THREADS: 512 / 768 = threads of the packet kernel where both shapes exist (0: the default, dc_kernelplan.h)
   bool bend_rows = true;    // DC_BEND_ROWS=0: a mesh whose flaps are all flat at rest keeps the per-flap passes too (dc_windows.h: rows)
 };
 
@@ -38,6 +39,7 @@ struct HostTables {
   int pk_ofs = 0;                      // pk is in the byte-offset layout (dc_packets.h): the kernel that runs holds the direction as halves
   int defl_rows = 0;                   // row padding of the deflation tables: the packet kernel's rows, or N rounded up to 64; 0 = no space wanted
   int fwd_defl = 0, adj_coarse = 0;    // set_deflation
+  bool defl_built = false;             // set_deflation: the context has a deflation space
   int dense_ld = 0;                    // explicit inverse (dense): its leading dimension, 0 = not built
   int self_cap = 0, self_lds = 1;
   float max_radii = 0.f;
@@ -59,6 +61,8 @@ struct HostTables {
   void build(const HostSystem &H, const dc_params &p, const TableSwitches &sw);
   // `built`: the context has a deflation space for defl_rows rows
   void set_deflation(bool built, const TableSwitches &sw);
+  // the decisions as the kernel choices of dc_kernelplan.h take them (after set_deflation)
+  PlanFacts facts(int N) const;
 };
 
 }  // namespace dc

@@ -57,6 +57,21 @@ def test_launch_plan_sizes_offsets_and_limits_of_the_dynamic_lds(tmp_path):
     assert r.returncode == 0 and r.stdout.strip().endswith("ALL OK"), r.stdout + r.stderr
 
 
+def test_kernel_plan_names_a_compiled_instance_for_every_mesh_size_and_switch(tmp_path):
+    """csrc/dc_kernelplan.h, the host-side plan of which kernel instance runs a step (tests/native/kernel_plan_check.cpp): the forward choice
+    (family, threads, rows, XL, halves, offsets, inverse, deflated, fusable) against answers written out by hand at every mesh size where it
+    changes, on the decisions HostTables::build takes on generated meshes, under the switches that move it; the adjoint's five conditions in
+    every combination; for every N up to 13 000 and every switch combination the choice names an entry of the instance tables, fusable <=> a
+    packet family, pk_ofs <=> the instance reads byte offsets, fwd_defl => a deflated instance; every accepted split plan has its instances."""
+    csrc = os.path.join(ROOT, "diffcloth_amd", "csrc")
+    exe = str(tmp_path / "kernel_plan_check")
+    srcs = [os.path.join(ROOT, "tests", "native", "kernel_plan_check.cpp")] + [os.path.join(csrc, f) for f in ("dc_tables.cpp", "dc_clusterplan.cpp", "dc_system.cpp", "dc_windows.cpp", "dc_packets.cpp", "dc_dense.cpp")]
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-I", csrc, "-o", exe] + srcs)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ALL OK"), r.stdout + r.stderr
+
+
 def test_deflation_builder_finds_the_lowest_eigenvectors(tmp_path):
     """csrc/dc_deflate.cpp on a synthetic badly graded strip (cells shrinking 100 x across the sheet): the Chebyshev-filtered subspace
     iteration returns orthonormal vectors whose eigen-residuals |A u - theta u| are small, (U^T A U)^-1 is consistent, in well under a
