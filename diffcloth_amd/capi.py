@@ -62,6 +62,9 @@ EXPORTED_SYMBOLS = [
     "dc_set_seed_schedule", "dc_clear_schedules", "dc_get_states", "dc_get_dxfixed", "dc_get_layout", "dc_get_packet_layout", "dc_get_bend_rows", "dc_comm_unique_id", "dc_comm_init", "dc_allreduce_sum", "dc_comm_destroy",
     "dc_get_deflation", "dc_set_record", "dc_set_trajectory_start", "dc_keep_force_gradients", "dc_get_force_gradients", "dc_use_stream", "dc_set_state_dev", "dc_get_state_dev", "dc_step_forward_dev", "dc_step_backward_dev",
     "dc_get_self_friction_path", "dc_get_adjoint_matrix", "dc_dense_phase_times",
+    "dc_rollout_forward_async", "dc_rollout_backward_async", "dc_set_fixed_point_schedule_dev", "dc_set_force_schedule_dev", "dc_set_seed_schedule_dev",
+    "dc_set_gradient_dev", "dc_get_gradient_dev", "dc_get_states_dev", "dc_get_dxfixed_dev", "dc_get_force_schedule_gradients_dev", "dc_set_mu_dev",
+    "dc_set_vertex_forces_dev",
 ]
 
 _lib = None
@@ -331,17 +334,31 @@ class Engine:
         return out
 
     # ---- device-pointer boundary (torch tensors on this GPU: no host copies, no synchronisation) ----
-    def _tp(self, t, per):
-        """(device pointer, is_f32) of a contiguous CUDA tensor of B * per elements, fp32 or fp64, on the engine's GPU"""
+    def _tp(self, t, per, lead=1):
+        """(device pointer, is_f32) of a contiguous CUDA tensor of lead * per elements, fp32 or fp64, on the engine's GPU; `lead` counts the
+        leading dimension of the whole-sweep calls (tape slots), 1 for the per-step ones"""
         dev = getattr(self, "device", None)
         import torch
         if t is None:
             return None, 1
         if t.is_cuda and dev is not None and t.device.index != dev:
             raise ValueError(f"tensor on cuda:{t.device.index}, the engine runs on device {dev}")
-        if not t.is_cuda or not t.is_contiguous() or t.dtype not in (torch.float32, torch.float64) or t.numel() != per:
-            raise ValueError(f"expected a contiguous CUDA float32 / float64 tensor of {per} elements, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        if not t.is_cuda or not t.is_contiguous() or t.dtype not in (torch.float32, torch.float64) or t.numel() != lead * per:
+            raise ValueError(f"expected a contiguous CUDA float32 / float64 tensor of {lead * per} elements, got {t.dtype} {tuple(t.shape)} on {t.device}")
         return C.c_void_p(t.data_ptr()), int(t.dtype == torch.float32)
+
+    def _tps(self, *specs):
+        """pointers of the tensors of ONE call, specs = (tensor or None, elements per slot, slots): they must share one dtype; returns
+        ([pointers], is_f32)"""
+        ptrs, kinds = [], set()
+        for t, per, lead in specs:
+            p, f = self._tp(t, per, lead)
+            ptrs.append(p)
+            if t is not None:
+                kinds.add(f)
+        if len(kinds) > 1:
+            raise ValueError("all tensors of a call must have one dtype")
+        return ptrs, (kinds.pop() if kinds else 1)
 
     def use_stream(self, stream=None):
         """run the context on a torch.cuda.Stream (None: back to its own stream)"""
@@ -384,6 +401,62 @@ class Engine:
 
     def rollout_backward(self, slot, nsteps):
         self._chk(self.lib.dc_rollout_backward(self.h, C.c_int(slot), C.c_int(nsteps)))
+
+    # ---- whole-sweep device-pointer boundary (torch tensors on this GPU; enqueued on the context's stream, nothing synchronises) ----
+    def rollout_forward_async(self, slot, nsteps):
+        """dc_rollout_forward without the wait (adds nothing to kernel_times; errors of the sweep surface at sync / get_stats)"""
+        self._chk(self.lib.dc_rollout_forward_async(self.h, C.c_int(slot), C.c_int(nsteps)))
+
+    def rollout_backward_async(self, slot, nsteps):
+        self._chk(self.lib.dc_rollout_backward_async(self.h, C.c_int(slot), C.c_int(nsteps)))
+
+    def set_fixed_point_schedule_dev(self, slot0, nsteps, xf):
+        """xf: [nsteps][B][3 Af] targets of the steps slot0+k -> slot0+k+1"""
+        (p,), f = self._tps((xf, self.B * 3 * self.Af, nsteps))
+        self._chk(self.lib.dc_set_fixed_point_schedule_dev(self.h, C.c_int(slot0), C.c_int(nsteps), p, C.c_int(f)))
+
+    def set_force_schedule_dev(self, slot0, nsteps, fu=None, fv_scale=None):
+        (pu, ps), f = self._tps((fu, self.B * 3, nsteps), (fv_scale, self.B, nsteps))
+        self._chk(self.lib.dc_set_force_schedule_dev(self.h, C.c_int(slot0), C.c_int(nsteps), pu, ps, C.c_int(f)))
+
+    def set_seed_schedule_dev(self, slot0, nslots, dL_dx=None, dL_dv=None):
+        """loss gradient w.r.t. the states at slots slot0 .. slot0+nslots-1, [nslots][B][3 N] each; None = zeros"""
+        n = self.B * 3 * self.N
+        (px, pv), f = self._tps((dL_dx, n, nslots), (dL_dv, n, nslots))
+        self._chk(self.lib.dc_set_seed_schedule_dev(self.h, C.c_int(slot0), C.c_int(nslots), px, pv, C.c_int(f)))
+
+    def set_gradient_dev(self, dL_dx, dL_dv):
+        n = self.B * 3 * self.N
+        (px, pv), f = self._tps((dL_dx, n, 1), (dL_dv, n, 1))
+        self._chk(self.lib.dc_set_gradient_dev(self.h, px, pv, C.c_int(f)))
+
+    def get_gradient_dev(self, dL_dx=None, dL_dv=None, dL_dmu=None):
+        n = self.B * 3 * self.N
+        (px, pv, pm), f = self._tps((dL_dx, n, 1), (dL_dv, n, 1), (dL_dmu, self.B * self.ngroups, 1))
+        self._chk(self.lib.dc_get_gradient_dev(self.h, px, pv, pm, C.c_int(f)))
+
+    def get_states_dev(self, slot0, nslots, x=None, v=None):
+        n = self.B * 3 * self.N
+        (px, pv), f = self._tps((x, n, nslots), (v, n, nslots))
+        self._chk(self.lib.dc_get_states_dev(self.h, C.c_int(slot0), C.c_int(nslots), px, pv, C.c_int(f)))
+
+    def get_dxfixed_dev(self, slot0, nslots, dxfixed):
+        (p,), f = self._tps((dxfixed, self.B * 3 * self.Af, nslots))
+        self._chk(self.lib.dc_get_dxfixed_dev(self.h, C.c_int(slot0), C.c_int(nslots), p, C.c_int(f)))
+
+    def get_force_schedule_gradients_dev(self, slot0, nslots, dfu=None, dfv_scale=None, dfv=None):
+        """gradients w.r.t. the force schedule of the steps through records slot0 .. slot0+nslots-1: dfu [nslots][B][3], dfv_scale
+        [nslots][B], dfv [B][3 N] (the last two need keep_force_gradients before the sweep)"""
+        (pu, ps, pv), f = self._tps((dfu, self.B * 3, nslots), (dfv_scale, self.B, nslots), (dfv, self.B * 3 * self.N, 1))
+        self._chk(self.lib.dc_get_force_schedule_gradients_dev(self.h, C.c_int(slot0), C.c_int(nslots), pu, ps, pv, C.c_int(f)))
+
+    def set_mu_dev(self, mu):
+        (p,), f = self._tps((mu, self.B * self.ngroups, 1))
+        self._chk(self.lib.dc_set_mu_dev(self.h, p, C.c_int(f)))
+
+    def set_vertex_forces_dev(self, fv):
+        (p,), f = self._tps((fv, self.B * 3 * self.N, 1))
+        self._chk(self.lib.dc_set_vertex_forces_dev(self.h, p, C.c_int(f)))
 
     # ---- device-resident schedules (dc_set_*_schedule) ----
     def set_gradient(self, dL_dx, dL_dv):

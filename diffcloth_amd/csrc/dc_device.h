@@ -242,5 +242,13 @@ void launch_dev_to_planar(const void *src, int is_f32, float *dst, int B, int n,
 void launch_planar_to_dev(const float *src, void *dst, int is_f32, int B, int n, const int *user_of, hipStream_t st);
 void launch_copy_cast(const float *src, void *dst, int is_f32, long total, hipStream_t st);
 void launch_seed_gradient(const float *x, const float *target, float *gx, float *gv, int B, int N, float scale, hipStream_t st);
+// the whole-sweep device-pointer boundary (dc_boundary.hip): `rows` = slots x rollouts consecutive [n][3] <-> [3][n] blocks in ONE launch,
+// 16 bytes per lane where n and the pointers allow it; small per-rollout data cast to fp32; the force-schedule gradients from the kept y tape
+void launch_rows_to_planar(const void *src, int is_f32, float *dst, long rows, int n, const int *user_of, hipStream_t st);
+void launch_planar_to_rows(const float *src, void *dst, int is_f32, long rows, int n, const int *user_of, hipStream_t st);
+void launch_cast_in(const void *src, int is_f32, float *dst, long total, hipStream_t st);
+void launch_dfu_from_param(const float *dpar, void *out, int is_f32, long rows, hipStream_t st);
+void launch_dfv_scale(const float *ys, const float *fv, void *out, int is_f32, int nslots, int B, int N, double h2, hipStream_t st);
+void launch_dfv(const float *ys, const float *w, void *out, int is_f32, int nslots, int B, int N, const int *user_of, double h2, hipStream_t st);
 
 }  // namespace dc

@@ -1482,6 +1482,162 @@ int dc_get_param_gradients(dc_ctx *c, int slot, double *out) {
   return DC_OK;
 }
 
+// ---- whole-sweep device-pointer boundary: the rollout calls, the schedule setters and the getters of a sweep's results for callers whose
+//      tensors live on this GPU (diffcloth_amd/functional.py: sim_rollout). Every buffer is a DEVICE pointer in the caller's layout, all slots
+//      of an array are converted in one launch (dc_boundary.hip), everything is enqueued on the context's stream and nothing synchronises.
+int dc_rollout_forward_async(dc_ctx *c, int slot, int nsteps) {
+  int rc = check_batch(c, slot, slot + nsteps);
+  if (rc) return rc;
+  if (nsteps < 1) return fail(c, DC_ERR_INVALID, "dc_rollout_forward_async: nsteps < 1");
+  HIPCHK(c, hipSetDevice(c->device));
+  return enqueue_forward_steps(c, slot, nsteps, true, nullptr);
+}
+
+int dc_rollout_backward_async(dc_ctx *c, int slot, int nsteps) {
+  int rc = check_batch(c, slot - nsteps + 1, slot);
+  if (rc) return rc;
+  if (nsteps < 1 || slot - nsteps + 1 < 1) return fail(c, DC_ERR_INVALID, "dc_rollout_backward_async: would run past slot 1");
+  HIPCHK(c, hipSetDevice(c->device));
+  return enqueue_backward_steps(c, slot, nsteps, Seeds::schedule, nullptr, nullptr);
+}
+
+int dc_set_fixed_point_schedule_dev(dc_ctx *c, int slot0, int nsteps, const void *d_xf, int is_f32) {
+  int rc = check_batch(c, slot0, slot0 + nsteps);
+  if (rc) return rc;
+  if (nsteps < 1 || !d_xf) return fail(c, DC_ERR_INVALID, "dc_set_fixed_point_schedule_dev: null schedule");
+  const int Af = c->S.Af;
+  if (Af <= 0) return DC_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  launch_rows_to_planar(d_xf, is_f32, xf_slot(c, slot0 + 1), (long) nsteps * c->B, Af, nullptr, c->stream);
+  HIPCHK(c, hipGetLastError());
+  for (int k = 1; k <= nsteps; k++) c->sched_xf[slot0 + k] = 1;
+  return DC_OK;
+}
+
+int dc_set_force_schedule_dev(dc_ctx *c, int slot0, int nsteps, const void *d_fu, const void *d_fv_scale, int is_f32) {
+  int rc = check_batch(c, slot0, slot0 + nsteps);
+  if (rc) return rc;
+  if (nsteps < 1) return fail(c, DC_ERR_INVALID, "dc_set_force_schedule_dev: nsteps < 1");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (d_fu) launch_cast_in(d_fu, is_f32, c->FU_S + (size_t) c->B * 3 * (slot0 + 1), (long) nsteps * c->B * 3, c->stream);
+  if (d_fv_scale) launch_cast_in(d_fv_scale, is_f32, c->FVS_S + (size_t) c->B * (slot0 + 1), (long) nsteps * c->B, c->stream);
+  HIPCHK(c, hipGetLastError());
+  for (int k = 1; k <= nsteps; k++) { c->sched_fu[slot0 + k] = d_fu ? 1 : 0; c->sched_fvs[slot0 + k] = d_fv_scale ? 1 : 0; }
+  return DC_OK;
+}
+
+int dc_set_seed_schedule_dev(dc_ctx *c, int slot0, int nslots, const void *d_dL_dx, const void *d_dL_dv, int is_f32) {
+  int rc = check_batch(c, slot0, slot0 + nslots - 1);
+  if (rc) return rc;
+  if (nslots < 1) return fail(c, DC_ERR_INVALID, "dc_set_seed_schedule_dev: nslots < 1");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t se = slot_elems(c), slots = (size_t) c->tape + 1;
+  if (!c->SEEDX) {
+    if ((rc = dev_alloc(c, c->batch_allocs, &c->SEEDX, se * slots))) return rc;
+    if ((rc = dev_alloc(c, c->batch_allocs, &c->SEEDV, se * slots))) return rc;
+  }
+  const long rows = (long) nslots * c->B;
+  if (d_dL_dx) launch_rows_to_planar(d_dL_dx, is_f32, seedx_slot(c, slot0), rows, c->host.N, c->d_user_of, c->stream);
+  else HIPCHK(c, hipMemsetAsync(seedx_slot(c, slot0), 0, se * nslots * sizeof(float), c->stream));
+  if (d_dL_dv) launch_rows_to_planar(d_dL_dv, is_f32, seedv_slot(c, slot0), rows, c->host.N, c->d_user_of, c->stream);
+  else HIPCHK(c, hipMemsetAsync(seedv_slot(c, slot0), 0, se * nslots * sizeof(float), c->stream));
+  HIPCHK(c, hipGetLastError());
+  for (int k = 0; k < nslots; k++) c->sched_seed[slot0 + k] = 1;
+  return DC_OK;
+}
+
+int dc_set_gradient_dev(dc_ctx *c, const void *d_dL_dx, const void *d_dL_dv, int is_f32) {
+  int rc = check_batch(c, 0, 0);
+  if (rc) return rc;
+  if (!d_dL_dx || !d_dL_dv) return fail(c, DC_ERR_INVALID, "dc_set_gradient_dev: null gradient");
+  HIPCHK(c, hipSetDevice(c->device));
+  launch_rows_to_planar(d_dL_dx, is_f32, c->GX, c->B, c->host.N, c->d_user_of, c->stream);
+  launch_rows_to_planar(d_dL_dv, is_f32, c->GV, c->B, c->host.N, c->d_user_of, c->stream);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemsetAsync(c->DMU, 0, sizeof(float) * c->B * c->S.ngroups, c->stream));
+  return DC_OK;
+}
+
+int dc_get_gradient_dev(dc_ctx *c, void *d_dL_dx, void *d_dL_dv, void *d_dL_dmu, int is_f32) {
+  int rc = check_batch(c, 0, 0);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (d_dL_dx) launch_planar_to_rows(c->GX, d_dL_dx, is_f32, c->B, c->host.N, c->d_user_of, c->stream);
+  if (d_dL_dv) launch_planar_to_rows(c->GV, d_dL_dv, is_f32, c->B, c->host.N, c->d_user_of, c->stream);
+  if (d_dL_dmu) launch_copy_cast(c->DMU, d_dL_dmu, is_f32, (long) c->B * c->S.ngroups, c->stream);
+  HIPCHK(c, hipGetLastError());
+  return DC_OK;
+}
+
+int dc_get_states_dev(dc_ctx *c, int slot0, int nslots, void *d_x, void *d_v, int is_f32) {
+  int rc = check_batch(c, slot0, slot0 + nslots - 1);
+  if (rc) return rc;
+  if (nslots < 1) return fail(c, DC_ERR_INVALID, "dc_get_states_dev: nslots < 1");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t se = slot_elems(c);
+  const long rows = (long) nslots * c->B;
+  if (d_x) launch_planar_to_rows(c->X + se * slot0, d_x, is_f32, rows, c->host.N, c->d_user_of, c->stream);
+  if (d_v) launch_planar_to_rows(c->V + se * slot0, d_v, is_f32, rows, c->host.N, c->d_user_of, c->stream);
+  HIPCHK(c, hipGetLastError());
+  return DC_OK;
+}
+
+int dc_get_dxfixed_dev(dc_ctx *c, int slot0, int nslots, void *d_dL_dxfixed, int is_f32) {
+  int rc = check_batch(c, slot0, slot0 + nslots - 1);
+  if (rc) return rc;
+  if (slot0 < 1 || nslots < 1 || !d_dL_dxfixed) return fail(c, DC_ERR_INVALID, "dc_get_dxfixed_dev: slot 0 has no record");
+  const int Af = c->S.Af;
+  if (Af <= 0) return DC_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  launch_planar_to_rows(dxf_slot(c, slot0), d_dL_dxfixed, is_f32, (long) nslots * c->B, Af, nullptr, c->stream);
+  HIPCHK(c, hipGetLastError());
+  return DC_OK;
+}
+
+int dc_get_force_schedule_gradients_dev(dc_ctx *c, int slot0, int nslots, void *d_dL_dfu, void *d_dL_dfv_scale, void *d_dL_dfv, int is_f32) {
+  int rc = check_batch(c, slot0, slot0 + nslots - 1);
+  if (rc) return rc;
+  if (slot0 < 1 || nslots < 1) return fail(c, DC_ERR_INVALID, "dc_get_force_schedule_gradients_dev: slot 0 has no record");
+  if ((d_dL_dfv_scale || d_dL_dfv) && !c->YS)
+    return fail(c, DC_ERR_STATE, "dc_get_force_schedule_gradients_dev: dc_keep_force_gradients(1) was not set before the backward sweep");
+  if (d_dL_dfv_scale && !c->fv_set) return fail(c, DC_ERR_STATE, "dc_get_force_schedule_gradients_dev: no per-vertex force is set (dc_set_vertex_forces)");
+  HIPCHK(c, hipSetDevice(c->device));
+  const double h2 = c->params.time_step * c->params.time_step;
+  const float *ys = c->YS ? c->YS + slot_elems(c) * slot0 : nullptr;
+  if (d_dL_dfu) launch_dfu_from_param(dpar_slot(c, slot0), d_dL_dfu, is_f32, (long) nslots * c->B, c->stream);
+  if (d_dL_dfv_scale) launch_dfv_scale(ys, c->fv, d_dL_dfv_scale, is_f32, nslots, c->B, c->host.N, h2, c->stream);
+  if (d_dL_dfv) {
+    // the factors of the steps through these records: the fv_scale schedule where one is set on all of them, else 1
+    int nfvs = 0;
+    for (int k = 0; k < nslots; k++) nfvs += c->sched_fvs[slot0 + k];
+    if (nfvs % nslots) return fail(c, DC_ERR_INVALID, "dc_get_force_schedule_gradients_dev: the fv_scale schedule covers only part of the slots");
+    launch_dfv(ys, nfvs ? c->FVS_S + (size_t) c->B * slot0 : nullptr, d_dL_dfv, is_f32, nslots, c->B, c->host.N, c->d_user_of, h2, c->stream);
+  }
+  HIPCHK(c, hipGetLastError());
+  return DC_OK;
+}
+
+int dc_set_mu_dev(dc_ctx *c, const void *d_mu, int is_f32) {
+  int rc = check_batch(c, 0, 0);
+  if (rc) return rc;
+  if (!d_mu) return fail(c, DC_ERR_INVALID, "dc_set_mu_dev: null mu (dc_set_mu(NULL) restores the defaults)");
+  HIPCHK(c, hipSetDevice(c->device));
+  launch_cast_in(d_mu, is_f32, c->mu, (long) c->B * c->S.ngroups, c->stream);
+  HIPCHK(c, hipGetLastError());
+  return DC_OK;
+}
+
+int dc_set_vertex_forces_dev(dc_ctx *c, const void *d_f, int is_f32) {
+  int rc = check_batch(c, 0, 0);
+  if (rc) return rc;
+  if (!d_f) { c->fv_set = false; return DC_OK; }
+  HIPCHK(c, hipSetDevice(c->device));
+  launch_rows_to_planar(d_f, is_f32, c->fv, c->B, c->host.N, c->d_user_of, c->stream);
+  HIPCHK(c, hipGetLastError());
+  c->fv_set = true;
+  return DC_OK;
+}
+
 int dc_get_stats(dc_ctx *c, int slot, dc_step_stats *fwd, dc_bwd_stats *bwd) {
   int rc = check_batch(c, slot, slot);
   if (rc) return rc;

@@ -10,6 +10,10 @@ step; here `x`, `v`, `a` carry a leading batch dimension and the step runs throu
     dL_dxinit / dL_dvinit (functional.py:66-75) — for that step the adjoint is the identity;
   * the gradient w.r.t. the action (fixed-point targets) is rescaled to a norm within [0.05, 4 * dim] per rollout
     (functional.py:88-97).
+`sim_rollout` is the whole-episode counterpart for open-loop problems (trajectory optimisation over clip targets, identification of mu
+or wind, any loss over all frames): one fused forward sweep and one fused backward sweep per evaluation, schedules and results crossing
+the boundary as device pointers (the whole-sweep dc_*_dev calls). Closed-loop controllers, whose action depends on the state of every
+step, stay on `sim_step`.
 CUDA tensors (fp32 or fp64) never leave the GPU: states, actions and gradients cross the boundary as device pointers
 (dc_*_dev of include/diffcloth_hip.h), the step is enqueued on torch's current stream and nothing synchronises — the
 reference copies every tensor through numpy on the host (functional.py:30-34, 60-64), which for B = 256 rollouts of 10 000
@@ -38,6 +42,7 @@ class BatchedSim:
         self._bwd_slots = set()
         self.strict = bool(strict)
         self.unconverged = 0
+        self._episode = 0              # counts sim_rollout episodes: a backward pass must find the tape of ITS forward pass
 
     def on_current_stream(self, device=None):
         """order the engine's work with torch's current CUDA stream of the tensors' device (once per stream change). torch's default
@@ -160,3 +165,186 @@ def sim_step(sim, x, v, a):
     """One differentiable time step of all rollouts: (x', v') = step(x, v; a). x, v: [B, 3N]; a: [B, 3 Af] clip targets.
     CUDA tensors stay on the GPU (device-pointer boundary); CPU tensors go through the host path."""
     return BatchedSimFunction.apply(x, v, a, sim)
+
+
+# ---- a whole episode as ONE differentiable function ------------------------------------------------------------------------------
+_ROLLOUT_INPUTS = ("x0", "v0", "actions", "uniform_force", "vertex_force_scale", "vertex_forces", "mu")
+
+
+def _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu):
+    """Checks the arguments of sim_rollout against the engine's sizes and returns the episode length T. Touches no device."""
+    e = sim.engine
+    B, N, Af, G = e.B, e.N, e.Af, e.ngroups
+    given = dict(zip(_ROLLOUT_INPUTS, (x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu)))
+    if x0 is None or v0 is None:
+        raise ValueError("sim_rollout: x0 and v0 are required")
+    for name, t in given.items():
+        if t is None:
+            continue
+        if not torch.is_tensor(t):
+            raise ValueError(f"sim_rollout: {name} must be a torch tensor")
+        if t.dtype != x0.dtype:
+            raise ValueError(f"sim_rollout: mixed dtypes: {name} is {t.dtype}, x0 is {x0.dtype}")
+        if t.device != x0.device:
+            raise ValueError(f"sim_rollout: mixed devices: {name} is on {t.device}, x0 on {x0.device}")
+    if x0.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"sim_rollout: float32 or float64 tensors, got {x0.dtype}")
+    if x0.is_cuda and getattr(e, "device", None) is not None and x0.device.index != e.device:
+        raise ValueError(f"sim_rollout: tensors on {x0.device}, the engine runs on device {e.device}")
+    if actions is not None and Af == 0:
+        raise ValueError("sim_rollout: actions given, but the scene has no attached vertices (Af == 0)")
+    if vertex_force_scale is not None and vertex_forces is None:
+        raise ValueError("sim_rollout: vertex_force_scale given without vertex_forces (the field the factors apply to)")
+    T = None
+    for name in ("actions", "uniform_force", "vertex_force_scale"):
+        if given[name] is not None and given[name].dim() > 0:
+            T = int(given[name].shape[0])
+            break
+    if T is None:
+        if steps is None:
+            raise ValueError("sim_rollout: no schedule given, pass steps=")
+        T = int(steps)
+    elif steps is not None and int(steps) != T:
+        raise ValueError(f"sim_rollout: steps = {steps}, but the first schedule has {T} steps")
+    if T < 1:
+        raise ValueError("sim_rollout: an episode has at least one step")
+    want = dict(x0=(B, 3 * N), v0=(B, 3 * N), actions=(T, B, 3 * Af), uniform_force=(T, B, 3), vertex_force_scale=(T, B),
+                vertex_forces=(B, 3 * N), mu=(B, G))
+    for name, t in given.items():
+        if t is not None and tuple(t.shape) != want[name]:
+            raise ValueError(f"sim_rollout: wrong shape: {name} is {tuple(t.shape)}, expected {want[name]}")
+    if T > e.tape:
+        raise RuntimeError(f"sim_rollout: an episode of {T} steps needs tape slots 0 .. {T}, the batch was allocated with tape = {e.tape}")
+    return T
+
+
+def _np64(t):
+    return None if t is None else t.detach().double().contiguous().numpy()
+
+
+class RolloutFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sim, T, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu):
+        e = sim.engine
+        B, N = e.B, e.N
+        sim._episode += 1
+        ctx.sim, ctx.T, ctx.episode = sim, T, sim._episode
+        ctx.save_for_backward(vertex_forces, vertex_force_scale)
+        sim._bwd_slots = set()
+        if x0.is_cuda:          # device path: every array of the episode crosses as a device pointer, on torch's stream
+            sim.on_current_stream(x0.device)
+            c = lambda t: None if t is None else t.detach().contiguous()
+            e.set_trajectory_start(0)
+            e.clear_schedules()
+            e.set_state_dev(0, c(x0), c(v0))
+            if mu is not None:
+                e.set_mu_dev(c(mu))
+            if vertex_forces is not None:
+                e.set_vertex_forces_dev(c(vertex_forces))
+            if actions is not None:
+                e.set_fixed_point_schedule_dev(0, T, c(actions))
+            if uniform_force is not None or vertex_force_scale is not None:
+                e.set_force_schedule_dev(0, T, fu=c(uniform_force), fv_scale=c(vertex_force_scale))
+            e.rollout_forward_async(0, T)
+            xs = torch.empty((T, B, 3 * N), dtype=x0.dtype, device=x0.device)
+            vs = torch.empty_like(xs)
+            e.get_states_dev(1, T, xs, vs)
+            sim.step_idx = T
+            return xs, vs
+        e.set_trajectory_start(0)
+        e.clear_schedules()
+        e.set_state(0, _np64(x0), _np64(v0))
+        if mu is not None:
+            e.set_mu(_np64(mu))
+        if vertex_forces is not None:
+            e.set_vertex_forces(_np64(vertex_forces))
+        if actions is not None:
+            e.set_fixed_point_schedule(0, _np64(actions))
+        if uniform_force is not None or vertex_force_scale is not None:
+            e.set_force_schedule(0, T, fu=_np64(uniform_force), fv_scale=_np64(vertex_force_scale))
+        e.rollout_forward(0, T)
+        xs, vs = e.get_states(1, T)
+        sim.step_idx = T
+        return torch.as_tensor(xs).to(x0.dtype), torch.as_tensor(vs).to(x0.dtype)
+
+    @staticmethod
+    def backward(ctx, grad_xs, grad_vs):
+        sim, T = ctx.sim, ctx.T
+        e = sim.engine
+        B, N, Af, G = e.B, e.N, e.Af, e.ngroups
+        if ctx.episode != sim._episode:
+            raise RuntimeError("sim_rollout: the tape holds a later episode; back-propagate an episode before the next sim_rollout on this BatchedSim")
+        vertex_forces, vertex_force_scale = ctx.saved_tensors
+        _, _, _, _, need_a, need_fu, need_fvs, need_fv, need_mu = ctx.needs_input_grad
+        keep = bool(need_fvs or need_fv)
+        sim._bwd_slots.update(range(1, T + 1))
+        dt = grad_xs.dtype
+        if grad_xs.is_cuda:
+            dev = grad_xs.device
+            sim.on_current_stream(dev)
+            gxs = grad_xs.detach().contiguous(); gvs = grad_vs.detach().to(dt).contiguous()
+            e.keep_force_gradients(keep)
+            e.set_seed_schedule_dev(0, 1)                                # the loss does not see the initial state: zeros
+            if T > 1:
+                e.set_seed_schedule_dev(1, T - 1, gxs[:T - 1], gvs[:T - 1])
+            e.set_gradient_dev(gxs[T - 1], gvs[T - 1])
+            e.rollout_backward_async(T, T)
+            new = lambda *shape: torch.empty(shape, dtype=dt, device=dev)
+            dx0, dv0 = new(B, 3 * N), new(B, 3 * N)
+            dmu = new(B, G) if need_mu else None
+            e.get_gradient_dev(dx0, dv0, dmu)
+            da = None
+            if need_a:
+                da = new(T, B, 3 * Af)
+                e.get_dxfixed_dev(1, T, da)
+            dfu = new(T, B, 3) if need_fu else None
+            dfvs = new(T, B) if need_fvs else None
+            dfv = new(B, 3 * N) if need_fv else None
+            if need_fu or keep:
+                e.get_force_schedule_gradients_dev(1, T, dfu=dfu, dfv_scale=dfvs, dfv=dfv)
+            sim.check_episode()                # the single synchronisation of the episode: errors of both sweeps surface here
+            return None, None, dx0, dv0, da, dfu, dfvs, dfv, dmu
+        gxs, gvs = _np64(grad_xs), _np64(grad_vs)
+        e.keep_force_gradients(keep)
+        zero = np.zeros((1, B, 3 * N))
+        e.set_seed_schedule(0, np.concatenate([zero, gxs[:T - 1]]), np.concatenate([zero, gvs[:T - 1]]))
+        e.set_gradient(gxs[T - 1], gvs[T - 1])
+        e.rollout_backward(T, T)
+        dx0, dv0, dmu = e.get_gradient()
+        t = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(dt)
+        da = t(e.get_dxfixed(1, T)) if need_a else None
+        dfu = t(np.stack([e.get_param_gradients(s)["sum_dfext"] for s in range(1, T + 1)])) if need_fu else None
+        dfvs = dfv = None
+        if keep:                               # the force-schedule reductions of the host path: numpy, fp64
+            y = e.get_force_gradients(1, T)    # h^2 y of every step, [T][B][3 N]
+            if need_fvs:
+                dfvs = t(np.einsum("kbq,bq->kb", y, _np64(vertex_forces)))
+            if need_fv:
+                w = np.ones((T, B)) if vertex_force_scale is None else _np64(vertex_force_scale)
+                dfv = t(np.einsum("kb,kbq->bq", w, y))
+        sim.check_episode()
+        return None, None, t(dx0), t(dv0), da, dfu, dfvs, dfv, (t(dmu) if need_mu else None)
+
+
+def sim_rollout(sim, x0, v0, actions=None, *, steps=None, uniform_force=None, vertex_force_scale=None, vertex_forces=None, mu=None):
+    """A whole differentiable episode of all rollouts: the states after every step, (xs, vs), [T, B, 3N] each in the dtype of x0.
+
+    x0, v0: [B, 3N] initial state. actions: [T, B, 3 Af] clip targets of every step. uniform_force: [T, B, 3] force on every vertex per
+    step. vertex_forces: [B, 3N] per-vertex force field, vertex_force_scale: [T, B] its factor per step (1 when omitted; the field is the
+    factor-free one). mu: [B, G] friction coefficient per primitive group. T comes from the first schedule given, or from `steps`.
+    Gradients flow to every tensor argument that requires one.
+
+    The episode occupies tape slots 0 .. T (T <= the tape of alloc_batch) and replaces what the tape held: the function sets the trajectory
+    start to slot 0, clears the schedules it does not set, and leaves sim.step_idx = T. `mu` and `vertex_forces`, when given, stay set on
+    the engine as after Engine.set_mu / set_vertex_forces; when omitted the engine's current values apply, as does its current uniform
+    force when there is no uniform_force schedule. An episode is back-propagated before the next sim_rollout on the same BatchedSim.
+
+    CUDA tensors: the state and the schedules are uploaded by the dc_*_dev setters, one fused forward sweep, one conversion of the states of
+    slots 1 .. T; backward: the incoming gradients become the seed schedule (slot 0 zeros, slots 1 .. T-1 grad[:-1]) and the carried
+    gradient (grad[-1]), one fused backward sweep, every gradient comes back on the device; all on torch's current stream. The only
+    synchronisation of the episode is BatchedSim.check_episode at the end of backward. CPU tensors take the host calls (float64 arrays).
+
+    The action gradient is dL_dxfixed of every step as the adjoint gives it: it is NOT rescaled. The clamp of its norm belongs to
+    `sim_step`, which mirrors the reference's per-step function (functional.py:88-97)."""
+    T = _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu)
+    return RolloutFunction.apply(sim, T, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu)

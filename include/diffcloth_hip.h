@@ -322,6 +322,44 @@ int dc_clear_schedules(dc_ctx *ctx);
 int dc_get_states(dc_ctx *ctx, int slot0, int nslots, double *x, double *v);
 /* dL_dxfixed of the steps through records slot0 .. slot0+nslots-1 of the last backward sweep / step (B*3Af each) */
 int dc_get_dxfixed(dc_ctx *ctx, int slot0, int nslots, double *dL_dxfixed /*nslots*B*3Af*/);
+/* ---- device-pointer boundary of whole sweeps: a loss + gradient evaluation over an episode for callers whose tensors live on this GPU
+ * (diffcloth_amd/functional.py: sim_rollout — trajectory optimisation over clip targets, identification of mu or wind, any loss over all
+ * frames: the host loop of Simulation::runBackwardTask, Simulation.cpp:3853-3961, with nothing crossing PCIe). The conventions of the
+ * per-step dc_*_dev calls hold: every buffer is a DEVICE pointer in the caller's layout — xyz interleaved, rollouts concatenated, slots
+ * concatenated, fp32 (is_f32 = 1) or fp64 (0), any element alignment — all slots of an array are converted by ONE kernel, the call is
+ * enqueued on the context's stream (dc_use_stream) and returns at once: no host copy, no synchronisation. Slot ranges and states are
+ * checked as in the host versions; a host-only context fails with DC_ERR_STATE.                                                       */
+/* dc_rollout_forward / dc_rollout_backward without the wait: the same checks and the same launches, enqueued only. They add NOTHING to
+ * dc_kernel_times (no event is read), and what a sweep reports after it has run — a timed-out exchange of the split kernels, a
+ * self-contact overflow — surfaces at the next dc_sync / dc_get_stats, as for the per-step dc_*_dev calls.                            */
+int dc_rollout_forward_async(dc_ctx *ctx, int slot, int nsteps);
+int dc_rollout_backward_async(dc_ctx *ctx, int slot, int nsteps);
+/* dc_set_fixed_point_schedule / dc_set_force_schedule (either force pointer may be NULL, as there) from device buffers */
+int dc_set_fixed_point_schedule_dev(dc_ctx *ctx, int slot0, int nsteps, const void *d_xf /*nsteps*B*3Af*/, int is_f32);
+int dc_set_force_schedule_dev(dc_ctx *ctx, int slot0, int nsteps, const void *d_fu /*nsteps*B*3 or NULL*/, const void *d_fv_scale /*nsteps*B or NULL*/, int is_f32);
+/* dc_set_seed_schedule from device buffers. A NULL d_dL_dx or d_dL_dv means zeros for those slots: a loss that does not touch some states
+ * still gives the complete schedule a fused sweep asks for.                                                                          */
+int dc_set_seed_schedule_dev(dc_ctx *ctx, int slot0, int nslots, const void *d_dL_dx /*nslots*B*3N or NULL*/, const void *d_dL_dv /*or NULL*/, int is_f32);
+/* dc_set_gradient (clears the accumulated dL_dmu as well) and dc_get_gradient (any pointer may be NULL) */
+int dc_set_gradient_dev(dc_ctx *ctx, const void *d_dL_dx /*B*3N*/, const void *d_dL_dv /*B*3N*/, int is_f32);
+int dc_get_gradient_dev(dc_ctx *ctx, void *d_dL_dx /*B*3N or NULL*/, void *d_dL_dv /*B*3N or NULL*/, void *d_dL_dmu /*B*num_groups or NULL*/, int is_f32);
+/* dc_get_states (either pointer may be NULL) and dc_get_dxfixed */
+int dc_get_states_dev(dc_ctx *ctx, int slot0, int nslots, void *d_x /*nslots*B*3N or NULL*/, void *d_v /*nslots*B*3N or NULL*/, int is_f32);
+int dc_get_dxfixed_dev(dc_ctx *ctx, int slot0, int nslots, void *d_dL_dxfixed /*nslots*B*3Af*/, int is_f32);
+/* Gradients w.r.t. the force schedule of the steps through records slot0 .. slot0 + nslots - 1 of the last backward sweep, reduced on the
+ * device; replaces reading dc_get_param_gradients per slot and dc_get_force_gradients (nslots*B*3N doubles) back to the host to form
+ * dL_dwindtimestep / dL_dconstantForceField there (Simulation.cpp:1700-1764). Any of the three may be NULL.
+ *   d_dL_dfu[k][b][0..2]   = elements 4..6 of that step's parameter gradients (h^2 sum_i y_i): gradient w.r.t. the step's uniform force
+ *   d_dL_dfv_scale[k][b]   = h^2 sum_{d,i} y[slot0+k][b][d][i] fv[b][d][i]: w.r.t. the step's factor on the dc_set_vertex_forces field
+ *   d_dL_dfv[b][3 i + d]   = h^2 sum_k w[k][b] y[slot0+k][b][d][i], w = the fv_scale schedule of those steps or 1 where none is set:
+ *                            w.r.t. the factor-free field; with w = 1 the reference's dL_dconstantForceField
+ * The last two read the kept y tape: DC_ERR_STATE without dc_keep_force_gradients(1) before the sweep, as dc_get_force_gradients.
+ * Sums are accumulated in fp64 in a fixed order without atomics and rounded once: bit-reproducible from run to run.                  */
+int dc_get_force_schedule_gradients_dev(dc_ctx *ctx, int slot0, int nslots, void *d_dL_dfu /*nslots*B*3 or NULL*/,
+                                        void *d_dL_dfv_scale /*nslots*B or NULL*/, void *d_dL_dfv /*B*3N or NULL*/, int is_f32);
+/* dc_set_mu (d_mu must not be NULL: dc_set_mu(NULL) restores the defaults) and dc_set_vertex_forces (NULL = none) from device buffers */
+int dc_set_mu_dev(dc_ctx *ctx, const void *d_mu /*B*num_groups*/, int is_f32);
+int dc_set_vertex_forces_dev(dc_ctx *ctx, const void *d_f /*B*3N or NULL*/, int is_f32);
 /* Which tape slot holds the trajectory's INITIAL state (default 0): the backward step through record start_slot + 1 is the reference's isStart step
  * (Simulation.cpp:3947, :1534: dL_dx of the initial state takes no dL_dv / h term) in dc_rollout_backward. -1: this tape holds a LATER segment of a
  * trajectory — no step of it is the start. With it a trajectory can be run as a chain of fused segments over several contexts (e.g. one context per
