@@ -6,6 +6,7 @@
 import os
 import subprocess
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "diffcloth_amd", "csrc")
@@ -52,9 +53,16 @@ def build_engine(force=False, verbose=False):
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
+
+    def compile_one(cmd):
+        # An object is as new as the sources were when its compile STARTED: a header edited while the compiler runs (minutes, for the step
+        # kernels) must leave the object stale for the next call, so the object gets the start time as its time stamp.
+        t0 = time.time()
+        run(cmd)
+        os.utime(cmd[-1], (t0, t0))
     if jobs:
         with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as pool:
-            list(pool.map(run, jobs))
+            list(pool.map(compile_one, jobs))
     if jobs or not os.path.exists(LIB):
         run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB] + objs)
         with open(stamp, "w") as f:

@@ -117,6 +117,9 @@ struct AdjCtx {
   // per span vertex and application; ~1 600 of 10 000 vertices of the bench cloth are in contact). Null when the list does not fit.
   float *ylist;
   int nself_verts;
+  // one bit per vertex, mark[i] != 0, in LDS at the end of the list's room (k_adjoint_step builds it once per step; null when list and mask do not
+  // both fit, or without bending rows): how the per-vertex phase of the CG's operator learns that its own staged slot holds y_i and not z_i
+  const unsigned *cmask;
 };
 
 // w = dr_df^T z for the (block-diagonal) primitive contacts: Simulation::calculatedr_df (Simulation.cpp:700-711)
@@ -352,21 +355,35 @@ __device__ __forceinline__ void adjoint_operator(const DevSystem &S, const AdjCt
     if constexpr (PRE) {
       // the per-vertex operator takes y_i (attachment vertices only) from its own reads instead of the window's input plane: the per-vertex phase
       // then reads the result planes only and the next window stages without a barrier in between (dc_winlib.h, NOA)
-      struct VertInY { f3 z, d, y; float m; int a; };
+      // OWN (wave-uniform; a mesh with bending rows, the CG's application: d1 == zin, no preconditioner): the rows' gather reads the vertex's own
+      // staged slot anyway and the barrier above is taken, so z_i, its dot partner and y_i come from that slot — no global load of zin / d1 at the head
+      // of the phase's chain (24 B per vertex and application). Only at a contact vertex does the slot hold y_i != z_i: its bit in C.cmask (LDS) says
+      // so, and z_i is loaded there alone, ahead of the gather like every read of pre(). Same values, same order of the sums as the loads gave.
+      const bool own = YL && C.cmask != nullptr && d1 == zin && !precond && table_rows(S);
+      const unsigned *cmask = C.cmask;
+      struct VertInY { f3 z, d, y; float m; int a; bool c; };
       auto vert_sp = vert_with_pre_noa([&](int i) {
         VertInY q;
-        q.z = ld3(zin, i, N);
-        if (precond) q.z = q.z * S.dinv[i];
-        q.d = d1 ? ld3(d1, i, N) : mk(0, 0, 0);
         q.m = S.mass[i]; q.a = S.att_of_vertex[i];
-        q.y = mk(0, 0, 0);
-        if (q.a >= 0) q.y = mark[i] ? ld3(C.y, i, N) : q.z;
+        q.z = q.d = q.y = mk(0, 0, 0);
+        if (own) {
+          q.c = (cmask[i >> 5] >> (i & 31)) & 1u;
+          if (q.c) q.z = ld3(zin, i, N);
+        } else {
+          q.c = true;
+          q.z = ld3(zin, i, N);
+          if (precond) q.z = q.z * S.dinv[i];
+          if (d1) q.d = ld3(d1, i, N);
+          if (q.a >= 0) q.y = mark[i] ? ld3(C.y, i, N) : q.z;
+        }
         return q;
-      }, [&](int i, f3 sum, f3, const VertInY &q) {
-        f3 o = q.z * q.m + sum;
-        if (q.a >= 0) o = o + q.y * (h2 * S.k_att);   // attachment: dp/dx = 0 (AttachmentSpring.cpp:35-37)
+      }, [&](int i, f3 sum, f3 a, const VertInY &q) {
+        const f3 z = q.c ? q.z : a;
+        const f3 d = own ? z : q.d, y = own ? a : q.y;
+        f3 o = z * q.m + sum;
+        if (q.a >= 0) o = o + y * (h2 * S.k_att);   // attachment: dp/dx = 0 (AttachmentSpring.cpp:35-37)
         st3(out, i, N, o);
-        if (d1) a1 += dot(o, q.d);
+        if (d1) a1 += dot(o, d);
         a2 += dot(o, o);
       });
       element_windows<THREADS>(S, C.lds, stage_y, C.xnew, AdjTriOp{h2}, AdjBendOp{h2}, vert_sp);
@@ -693,7 +710,7 @@ __global__ __launch_bounds__(THREADS) void k_adjoint_step(const DevSystem *__res
   C.nself = (S.contact_enabled && S.self_enabled) ? A.self.meta[(size_t) b * kMetaStride] : 0;
   // the contact vertices of this step (the detection's cell / order arrays are free during the backward sweep)
   C.mark = A.dense_y ? nullptr : W.sd_cell + (size_t) b * N;
-  C.plist = nullptr; C.nplist = 0; C.ylist = nullptr; C.nself_verts = 0;
+  C.plist = nullptr; C.nplist = 0; C.ylist = nullptr; C.nself_verts = 0; C.cmask = nullptr;
   if (C.mark) {
     int *plist = W.sd_order + (size_t) b * N;
     __shared__ int nplist;
@@ -716,6 +733,20 @@ __global__ __launch_bounds__(THREADS) void k_adjoint_step(const DevSystem *__res
     C.plist = plist; C.nplist = nplist; C.nself_verts = M;
     C.ylist = (WIN && nplist + M <= A.ycap) ? dyn_lds + A.ybase : nullptr;
     __syncthreads();
+    // the contact mask of the own-slot form (adjoint_operator): one bit per vertex in the last words of the list's room, when the list leaves them
+    if constexpr (WIN && THREADS == 1024 && !BLK && !COARSE) {      // (the instances whose correction solves are CG's)
+      const int mwords = 2 * ((N + 63) >> 6);
+      if (C.ylist && table_rows(S) && 3 * (nplist + M) + mwords <= 3 * A.ycap) {
+        unsigned *cm = (unsigned *) (dyn_lds + A.ybase + 3 * A.ycap - mwords);
+        for (int i0 = 0; i0 < N; i0 += THREADS) {      // (N rounded up to whole waves: every wave of a round writes its two words)
+          const int i = i0 + tid;
+          const unsigned long long bal = __ballot(i < N && C.mark[i] != 0);
+          if ((tid & 63) == 0 && i < N) { cm[i >> 5] = (unsigned) bal; cm[(i >> 5) + 1] = (unsigned) (bal >> 32); }
+        }
+        C.cmask = cm;
+        __syncthreads();
+      }
+    }
   }
   float *gx = A.gx + off;
   float *gin = W.g + off, *u = W.vnow + off;

@@ -402,14 +402,28 @@ __device__ __forceinline__ bool apply_K64(const DevSystem &S, const Adj64 &C, Te
   if (!form_y64<THREADS>(S, C, tm, z, W.y)) return false;
   const int N = S.N, NC = S.NC, K = tm.parts(), part = tm.part();
   const auto Y = tm.yv(W.y), X = tm.yv(W.x), CV = tm.yv(W.corner, NC);
+  // Flat-rest bending as matrix rows (S.win_rows: every flap is in its linear branch, dc_windows.h): the flap range is empty, its part of the
+  // corner array is not touched, and the rows h^2 B_ij in fp64 (brow_*, CSR without the diagonal) enter in the vertex loop below — no corner
+  // written and read back for 4 E of the 3 T + 4 E entries. Without rows everything is what it was.
+  const bool rows = S.win_rows != 0 && S.brow_ptr != nullptr;
   element_pass64<THREADS>(S, X, Y, CV, (int) ((long long) S.T * part / K), (int) ((long long) S.T * (part + 1) / K),
-                          (int) ((long long) S.E * part / K), (int) ((long long) S.E * (part + 1) / K));
+                          rows ? 0 : (int) ((long long) S.E * part / K), rows ? 0 : (int) ((long long) S.E * (part + 1) / K));
   if (!tm.barrier()) return false;
   const double hk = S.h64 * S.h64 * S.k_att64;
+  const int flap0 = 3 * S.T;      // (a vertex's triangle corners precede its flap corners in inc_idx: dc_system.cpp)
   for (int i = tm.r0() + threadIdx.x; i < tm.r1(); i += THREADS) {
     d3 o = ld3d(z, i, N) * S.mass64[i];
     const int k1 = S.inc_ptr[i + 1];
-    for (int k = S.inc_ptr[i]; k < k1; k++) o = o + ld3y(CV, S.inc_idx[k], NC);
+    if (rows) {
+      for (int k = S.inc_ptr[i]; k < k1; k++) { const int c = S.inc_idx[k]; if (c >= flap0) break; o = o + ld3y(CV, c, NC); }
+      const d3 yi = ld3y(Y, i, N);
+      d3 b = mkd(0, 0, 0);
+      const int r1 = S.brow_ptr[i + 1];
+      for (int k = S.brow_ptr[i]; k < r1; k++) b = b + (ld3y(Y, S.brow_col[k], N) - yi) * S.brow_val[k];      // fixed order: columns ascending
+      o = o + b;
+    } else {
+      for (int k = S.inc_ptr[i]; k < k1; k++) o = o + ld3y(CV, S.inc_idx[k], NC);
+    }
     if (S.att_of_vertex[i] >= 0) o = o + ld3y(Y, i, N) * hk;       // attachment: dp/dx = 0 (AttachmentSpring.cpp:35-37)
     vert(i, o);
   }

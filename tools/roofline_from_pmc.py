@@ -49,7 +49,10 @@ def main(out, tag):
     fetch = counters(os.path.join(out, "pmc_FETCH_SIZE")); write = counters(os.path.join(out, "pmc_WRITE_SIZE"))
     sqb = counters(os.path.join(out, "pmc_sq_b")); sqc = counters(os.path.join(out, "pmc_sq_c"))
     res = {"tag": tag, "config_key": line["config"]["config_key"], "command": line.get("_command", ""),
-           "calibration": {f"{c}:{k}": v for (c, k), v in calib.items()}, "bench_value": line["value"], "kernels": {}}
+           "calibration": {f"{c}:{k}": v for (c, k), v in calib.items()},
+           # the factors hbm_bytes was formed with: measured by the calibration kernels above, or the defaults when no calibration pass ran
+           "calibration_used": {"FETCH_SIZE": f4, "WRITE_SIZE": w4, "source": "measured" if calib else "defaults (no calibration pass in this call)"},
+           "bench_value": line["value"], "kernels": {}}
     for ent in line["roofline"]["kernels"]:
         name, n = ent["kernel"], max(int(ent.get("launches", 1)), 1)
         fr, full = last(fetch, name, "FETCH_SIZE", n)
