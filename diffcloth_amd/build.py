@@ -2,6 +2,7 @@
 
   libdiffcloth_hip.so       C-ABI engine (include/diffcloth_hip.h): host system builder + HIP kernels
   libdc_dense_lu_check.so   test infrastructure (tests/native/dense_lu_check.hip): the dense adjoint solve's LU kernels on arbitrary matrices
+  libdc_band_lu_check.so    test infrastructure (tests/native/band_lu_check.hip): the band adjoint solve's LU kernels on arbitrary band matrices
 """
 import os
 import subprocess
@@ -15,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libdiffcloth_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-ENGINE_SOURCES = ["dc_forward.hip", "dc_forward_res.hip", "dc_forward_pk.hip", "dc_forward_pk_defl.hip", "dc_forward_cl.hip", "dc_forward_cl_defl.hip", "dc_adjoint.hip", "dc_adjoint_cl.hip", "dc_adjoint_dense.hip", "dc_selfcontact.hip", "dc_convert.hip", "dc_boundary.hip", "dc_engine.hip", "dc_comm.cpp", "dc_tables.cpp", "dc_clusterplan.cpp", "dc_record.cpp", "dc_system.cpp", "dc_windows.cpp", "dc_packets.cpp", "dc_dense.cpp", "dc_deflate.cpp", "dc_spheremesh.cpp"]
+ENGINE_SOURCES = ["dc_forward.hip", "dc_forward_res.hip", "dc_forward_pk.hip", "dc_forward_pk_defl.hip", "dc_forward_cl.hip", "dc_forward_cl_defl.hip", "dc_adjoint.hip", "dc_adjoint_cl.hip", "dc_adjoint_dense.hip", "dc_adjoint_band.hip", "dc_selfcontact.hip", "dc_convert.hip", "dc_boundary.hip", "dc_engine.hip", "dc_comm.cpp", "dc_tables.cpp", "dc_clusterplan.cpp", "dc_record.cpp", "dc_system.cpp", "dc_windows.cpp", "dc_packets.cpp", "dc_dense.cpp", "dc_deflate.cpp", "dc_spheremesh.cpp"]
 
 
 def _stale(target, deps):
@@ -89,7 +90,8 @@ def build_pymodule(force=False, verbose=False):
     return out
 
 
-KERNEL_CHECKS = {"libdc_dense_lu_check.so": ("dense_lu_check.hip", ["dc_adjoint_dense.hip"])}
+KERNEL_CHECKS = {"libdc_dense_lu_check.so": ("dense_lu_check.hip", ["dc_adjoint_dense.hip"]),
+                 "libdc_band_lu_check.so": ("band_lu_check.hip", ["dc_adjoint_band.hip"])}
 
 
 def kernel_check_path(name="libdc_dense_lu_check.so"):

@@ -61,7 +61,7 @@ EXPORTED_SYMBOLS = [
     "dc_timer_stop", "dc_kernel_times", "dc_get_cluster", "dc_set_gradient", "dc_set_fixed_point_schedule", "dc_set_force_schedule",
     "dc_set_seed_schedule", "dc_clear_schedules", "dc_get_states", "dc_get_dxfixed", "dc_get_layout", "dc_get_packet_layout", "dc_get_bend_rows", "dc_comm_unique_id", "dc_comm_init", "dc_allreduce_sum", "dc_comm_destroy",
     "dc_get_deflation", "dc_set_record", "dc_set_trajectory_start", "dc_keep_force_gradients", "dc_get_force_gradients", "dc_use_stream", "dc_set_state_dev", "dc_get_state_dev", "dc_step_forward_dev", "dc_step_backward_dev",
-    "dc_get_self_friction_path", "dc_get_adjoint_matrix", "dc_dense_phase_times",
+    "dc_get_self_friction_path", "dc_get_adjoint_matrix", "dc_dense_phase_times", "dc_set_adjoint_band", "dc_get_adjoint_band",
     "dc_rollout_forward_async", "dc_rollout_backward_async", "dc_set_fixed_point_schedule_dev", "dc_set_force_schedule_dev", "dc_set_seed_schedule_dev",
     "dc_set_gradient_dev", "dc_get_gradient_dev", "dc_get_states_dev", "dc_get_dxfixed_dev", "dc_get_force_schedule_gradients_dev", "dc_set_mu_dev",
     "dc_set_vertex_forces_dev",
@@ -167,10 +167,10 @@ class Engine:
         if backward_tol is not None: p.backward_tol = backward_tol
         if gradient_clipping is not None: p.gradient_clipping = int(gradient_clipping)
         if clip_threshold is not None: p.gradient_clipping_threshold = clip_threshold
-        # a direct solve asked for keeps the dense one (adjoint_mode 2), as dc_set_solver does
-        if force_direct_adjoint is not None: p.adjoint_mode = (2 if p.adjoint_mode == 2 else 1) if force_direct_adjoint else 0
+        # a direct solve asked for keeps the dense one (adjoint_mode 2) and the banded one (adjoint_mode 3), as dc_set_solver does
+        if force_direct_adjoint is not None: p.adjoint_mode = (p.adjoint_mode if p.adjoint_mode in (2, 3) else 1) if force_direct_adjoint else 0
         self._chk(self.lib.dc_set_solver(self.h, C.c_double(p.forward_tol), C.c_double(p.backward_tol), C.c_int(p.gradient_clipping),
-                                         C.c_double(p.gradient_clipping_threshold), C.c_int(int(p.adjoint_mode in (1, 2)))))
+                                         C.c_double(p.gradient_clipping_threshold), C.c_int(int(p.adjoint_mode in (1, 2, 3)))))
 
     def set_primitives(self, prims):
         """prims: list of dicts(kind, group, center, top_offset, radius, length, mu, rotates)."""
@@ -593,8 +593,19 @@ class Engine:
         self._chk(self.lib.dc_get_adjoint_matrix(self.h, C.c_int(slot), C.c_int(rollout), _d(K)))
         return K
 
+    def set_adjoint_band(self, extra_vertices):
+        """adjoint_mode 3: vertices added to the matrix bandwidth for self contacts that couple outside it (dc_set_adjoint_band)"""
+        self._chk(self.lib.dc_set_adjoint_band(self.h, C.c_int(int(extra_vertices))))
+
+    def adjoint_band(self):
+        """what adjoint_mode 3 would use for the built system (dc_get_adjoint_band; host-only contexts too): kl (= ku), ldab and the bytes of
+        band storage per rollout"""
+        kl = C.c_int(); ldab = C.c_int(); nbytes = C.c_longlong()
+        self._chk(self.lib.dc_get_adjoint_band(self.h, C.byref(kl), C.byref(ldab), C.byref(nbytes)))
+        return dict(kl=kl.value, ldab=ldab.value, bytes_per_rollout=nbytes.value)
+
     def dense_phase_times(self, reset=False):
-        """device ms of the mode-2 backward steps: (assembly, factorisation, solve); only with DC_DENSE_TIMES=1 (dc_dense_phase_times)"""
+        """device ms of the mode-2 / mode-3 backward steps: (assembly, factorisation, solve); only with DC_DENSE_TIMES=1 (dc_dense_phase_times)"""
         ms = (C.c_float * 3)()
         self._chk(self.lib.dc_dense_phase_times(self.h, ms, C.c_int(int(reset))))
         return tuple(float(v) for v in ms)

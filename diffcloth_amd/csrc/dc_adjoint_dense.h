@@ -32,6 +32,9 @@ struct DenseAdjWork {
 
 // K of rollouts b0 .. b0 + nb - 1 of the record A describes (A.nsteps must be 1); x64 = the rollouts' fp64 x_new scratch ([B][3][N], W.x64)
 void launch_dense_assemble(const DevSystem &S, const BwdArgs &A, double *x64, const DenseAdjWork &D, int b0, int nb, hipStream_t st);
+// the first kernel of launch_dense_assemble alone: x64 and D.pm / D.sg of the rollouts (D.K is not touched); the band solve's assembly
+// (dc_adjoint_band.h) starts from the same blocks
+void launch_dense_prep(const DevSystem &S, const BwdArgs &A, double *x64, const DenseAdjWork &D, int b0, int nb, hipStream_t st);
 // LU of the nb matrices in place; returns the number of kernel launches it enqueued
 int launch_dense_factor(const DenseAdjWork &D, int n, int nb, hipStream_t st);
 // the adjoint step of rollouts b0 .. b0 + nb - 1 with the factors of D

@@ -17,43 +17,13 @@
 #include "dc_adjprecond.h"
 #include "dc_adjoint64.h"
 #include "dc_adjoint_dense.h"
+#include "dc_adjoint_direct.h"
 
 namespace dc {
 
 constexpr int kDenseRefine = 3;        // substitutions (each followed by an fp64 residual) before the fp64 BiCGSTAB fall-back
 
 namespace {
-
-// Adj64 of rollout b for record A (as k_adjoint_step sets it up; no LDS: the layered self pass takes its global-memory path)
-__device__ __forceinline__ Adj64 dense_adj64(const DevSystem &S, const BwdArgs &A, int b) {
-  const int N = S.N;
-  const size_t off = (size_t) b * 3 * N;
-  Adj64 C;
-  C.xnew = A.x_new + off; C.rec_f = A.rec_f + off; C.rec_n = A.rec_n + off;
-  C.mu = A.mu + (size_t) b * S.ngroups;
-  C.xprev = A.x_prev + off; C.vnew = A.v_new + off;
-  C.rec_prim = A.rec_prim + (size_t) b * N;
-  C.self = A.self; C.b = b;
-  C.nself = (S.contact_enabled && S.self_enabled) ? A.self.meta[(size_t) b * kMetaStride] : 0;
-  C.lds = nullptr; C.lds_floats = 0;
-  adj64_inject(C, A, b, N, S.self_cap);
-  return C;
-}
-
-// One accessor type for the three vectors element_pass64 touches (it takes them as one template type): x_new (plain loads), a unit
-// vector y = e_u, and a corner sink that keeps the three components of corner `k` only.
-struct ProbeV {
-  int kind;                  // 0 = plain, 1 = unit vector, 2 = corner sink
-  const double *p;
-  int u, k, NC;
-  d3 *o;
-  __device__ __forceinline__ double ld(int idx) const { return kind == 0 ? p[idx] : (idx == u ? 1.0 : 0.0); }
-  __device__ __forceinline__ void st(int idx, double v) const {
-    if (idx == k) o->x = v;
-    else if (idx == NC + k) o->y = v;
-    else if (idx == 2 * NC + k) o->z = v;
-  }
-};
 
 // x_new in fp64 (xnew64, as prepare_x64 forms it), the primitive contacts' (I + dr_df)^T blocks and the self contacts' G blocks
 template <int THREADS>
@@ -174,11 +144,6 @@ __global__ __launch_bounds__(THREADS) void k_dense_assemble(const DevSystem *__r
   }
   const double m = S.mass64[i];
   for (int c = 0; c < 3; c++) K[(size_t) r[c] * ld + r[c]] += m;
-}
-
-// (value, row) maximum with ties to the lower row
-__device__ __forceinline__ void amax_merge(double &v, int &r, double v2, int r2) {
-  if (v2 > v || (v2 == v && r2 < r)) { v = v2; r = r2; }
 }
 
 // Panel [k0, k0 + kb) of one matrix, column by column: pivot search, row swap across the panel, scaling, rank-1 update of the rest of
@@ -445,6 +410,10 @@ __global__ __launch_bounds__(THREADS) void k_adjoint_dense_step(const DevSystem 
 void launch_dense_assemble(const DevSystem &S, const BwdArgs &A, double *x64, const DenseAdjWork &D, int b0, int nb, hipStream_t st) {
   hipLaunchKernelGGL(k_dense_prep<256>, dim3(nb), dim3(256), 0, st, S.self_dev, A, x64, D, b0);
   hipLaunchKernelGGL(k_dense_assemble<64>, dim3((S.N + 63) / 64, nb), dim3(64), 0, st, S.self_dev, A, (const double *) x64, D, b0);
+}
+
+void launch_dense_prep(const DevSystem &S, const BwdArgs &A, double *x64, const DenseAdjWork &D, int b0, int nb, hipStream_t st) {
+  hipLaunchKernelGGL(k_dense_prep<256>, dim3(nb), dim3(256), 0, st, S.self_dev, A, x64, D, b0);
 }
 
 int launch_dense_factor(const DenseAdjWork &D, int n, int nb, hipStream_t st) {

@@ -10,6 +10,7 @@
 #include "dc_deflate.h"
 #include "dc_cluster.h"
 #include "dc_adjoint_dense.h"
+#include "dc_adjoint_band.h"
 
 // Tables of the split kernels (dc_cluster.h) for one K, built when the batch size is known (dc_alloc_batch).
 struct ClusterSet {
@@ -104,6 +105,12 @@ struct dc_ctx {
   bool dense_timing = false;
   float dense_ms[3] = {0, 0, 0};
   hipEvent_t ev_d[4] = {nullptr, nullptr, nullptr, nullptr};
+  // banded direct adjoint solve (adjoint_mode 3, dc_adjoint_band.h): bands / factors of a chunk of band_nb rollouts, in a pool of their own
+  // (dc_set_adjoint_band changes their size: re-allocated at the next mode-3 backward step); counters, timing and events are mode 2's
+  dc::BandAdjWork band{};
+  int band_nb = 0;
+  int band_extra = 0;               // dc_set_adjoint_band: vertices added to the matrix bandwidth
+  std::vector<void *> band_allocs;
 };
 
 inline int fail(dc_ctx *c, int code, const std::string &msg) {

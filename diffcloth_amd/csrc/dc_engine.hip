@@ -322,6 +322,18 @@ int check_dense_mode(dc_ctx *c, int mode, int N, const char *who) {
   return DC_OK;
 }
 
+// adjoint_mode 3 keeps K of a rollout in band storage: the one rule of dc_bandplan.h (band bytes within the chunk budget, the step kernel's
+// right-hand side and panel block within a workgroup's LDS). The matrix bandwidth is known once dc_build has planned the tables.
+int check_band_mode(dc_ctx *c, int mode, int extra, const char *who) {
+  if (mode != 3) return DC_OK;
+  const BandPlan bp = band_plan(c->host.N, c->bandwidth, extra);
+  if (bp.ok) return DC_OK;
+  return fail(c, DC_ERR_INVALID, std::string(who) + ": adjoint_mode 3 (banded direct adjoint solve) does not take this mesh (" + std::to_string(c->host.N) +
+              " vertices, matrix bandwidth " + std::to_string(c->bandwidth) + " + " + std::to_string(extra) + "): the band of one rollout needs " +
+              std::to_string(bp.bytes) + " bytes of the " + std::to_string(kBandBudgetBytes) + " allowed, the solve " + std::to_string(bp.lds_bytes) +
+              " bytes of LDS of the " + std::to_string(kBandLdsBytes) + " allowed");
+}
+
 // Scratch of the dense adjoint solve, on first use: as many rollouts per chunk as fit a budget of 8 GB (DC_DENSE_CHUNK=k caps the chunk at
 // k rollouts, development switch: the chunked path on small batches). DC_DENSE_FLAG=b, development switch read by enqueue_dense_adjoint:
 // rollout b is marked as if its factorisation had met a zero pivot (no valid scene does), so its adjoint step takes the fp64 BiCGSTAB
@@ -350,29 +362,56 @@ int dense_ensure(dc_ctx *c) {
   return DC_OK;
 }
 
-// one mode-2 backward step (A.nsteps == 1): per chunk of rollouts assemble K -> factor -> adjoint step with the factors
-int enqueue_dense_adjoint(dc_ctx *c, const BwdArgs &A) {
-  if (A.nsteps != 1) return fail(c, DC_ERR_INVALID, "adjoint_mode 2 runs one backward step per launch");
+// Scratch of the band adjoint solve, on first use and again after dc_set_adjoint_band changed the band: chunks under the dense solve's budget
+// and switches (DC_DENSE_CHUNK, DC_DENSE_TIMES; DC_DENSE_FLAG in enqueue_dense_adjoint).
+int band_ensure(dc_ctx *c) {
   int rc;
-  if ((rc = dense_ensure(c))) return rc;
-  const DenseAdjWork &D = c->dense;
-  const int n = 3 * c->host.N;
+  if ((rc = check_band_mode(c, 3, c->band_extra, "adjoint_mode 3"))) return rc;
+  const BandPlan bp = band_plan(c->host.N, c->bandwidth, c->band_extra);
+  if (c->band.AB && c->band.kl == bp.kl) return DC_OK;
+  if (c->band.AB) HIPCHK(c, hipStreamSynchronize(c->stream));
+  free_pool(c->band_allocs);
+  c->band = BandAdjWork{};
+  const int N = c->host.N, n = 3 * N, cap = std::max(c->self_cap, 1);
+  BandAdjWork D{};
+  D.n = n; D.kl = bp.kl; D.ldab = bp.ldab; D.pld = band_pld(bp.kl); D.npiv = band_round16(n); D.sub_cols = bp.sub_cols;
+  const size_t per = (size_t) bp.bytes + (size_t) D.npiv * sizeof(int) + sizeof(int) + (size_t) 9 * N * sizeof(double) + (size_t) 9 * cap * sizeof(double) +
+                     (size_t) 2 * kBandPanel * D.pld * sizeof(double);
+  int nb = (int) std::max<size_t>(1, std::min<size_t>((size_t) c->B, (size_t) kBandBudgetBytes / per));
+  const int chunk = env_int("DC_DENSE_CHUNK", 0);
+  if (chunk > 0) nb = std::min(nb, chunk);
+  if ((rc = dev_alloc(c, c->band_allocs, &D.AB, (size_t) nb * D.ldab * n))) return rc;
+  if ((rc = dev_alloc(c, c->band_allocs, &D.piv, (size_t) nb * D.npiv))) return rc;
+  if ((rc = dev_alloc(c, c->band_allocs, &D.flag, (size_t) nb))) return rc;
+  if ((rc = dev_alloc(c, c->band_allocs, &D.pm, (size_t) nb * 9 * N))) return rc;
+  if ((rc = dev_alloc(c, c->band_allocs, &D.sg, (size_t) nb * 9 * cap))) return rc;
+  if ((rc = dev_alloc(c, c->band_allocs, &D.panel, (size_t) nb * 2 * kBandPanel * D.pld))) return rc;
+  c->band = D;
+  c->band_nb = nb;
+  c->dense_timing = env_on("DC_DENSE_TIMES", false);
+  if (c->dense_timing)
+    for (auto &e : c->ev_d) if (!e) HIPCHK(c, hipEventCreate(&e));
+  return DC_OK;
+}
+
+// one mode-2 or mode-3 backward step (A.nsteps == 1): per chunk of rollouts assemble K -> factor -> adjoint step with the factors. The
+// chunk loop, DC_DENSE_FLAG and DC_DENSE_TIMES are the same for both; the modes differ in the three launches (`launch3`: phase 0 / 1 / 2 of
+// rollouts b0 .. b0 + nb - 1, adding its kernel launches to c->dense_launches).
+template <typename Launch3>
+int direct_adjoint_chunks(dc_ctx *c, int chunk_nb, int *flag, Launch3 launch3) {
   static const int one = 1;
   const int forced = env_int("DC_DENSE_FLAG", -1);
-  for (int b0 = 0; b0 < c->B; b0 += c->dense_nb) {
-    const int nb = std::min(c->dense_nb, c->B - b0);
+  for (int b0 = 0; b0 < c->B; b0 += chunk_nb) {
+    const int nb = std::min(chunk_nb, c->B - b0);
     if (c->dense_timing) HIPCHK(c, hipEventRecord(c->ev_d[0], c->stream));
-    HIPCHK(c, hipMemsetAsync(D.flag, 0, sizeof(int) * nb, c->stream));
-    if (forced >= b0 && forced < b0 + nb) HIPCHK(c, hipMemcpyAsync(D.flag + (forced - b0), &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    launch_dense_assemble(c->S, A, c->W.x64, D, b0, nb, c->stream);
-    if (c->dense_timing) HIPCHK(c, hipEventRecord(c->ev_d[1], c->stream));
-    c->dense_launches += 2 + launch_dense_factor(D, n, nb, c->stream);
-    if (c->dense_timing) HIPCHK(c, hipEventRecord(c->ev_d[2], c->stream));
-    launch_dense_adjoint_step(c->S, c->W, A, D, b0, nb, c->stream);
-    c->dense_launches += 1;
+    HIPCHK(c, hipMemsetAsync(flag, 0, sizeof(int) * nb, c->stream));
+    if (forced >= b0 && forced < b0 + nb) HIPCHK(c, hipMemcpyAsync(flag + (forced - b0), &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    for (int phase = 0; phase < 3; phase++) {
+      HIPCHK(c, launch3(phase, b0, nb));
+      if (c->dense_timing) HIPCHK(c, hipEventRecord(c->ev_d[phase + 1], c->stream));
+    }
     HIPCHK(c, hipGetLastError());
     if (c->dense_timing) {
-      HIPCHK(c, hipEventRecord(c->ev_d[3], c->stream));
       HIPCHK(c, hipEventSynchronize(c->ev_d[3]));
       for (int k = 0; k < 3; k++) {
         float ms = 0;
@@ -382,6 +421,29 @@ int enqueue_dense_adjoint(dc_ctx *c, const BwdArgs &A) {
     }
   }
   return DC_OK;
+}
+int enqueue_dense_adjoint(dc_ctx *c, const BwdArgs &A) {
+  const bool band = c->params.adjoint_mode == 3;
+  if (A.nsteps != 1) return fail(c, DC_ERR_INVALID, "adjoint_mode 2 / 3 runs one backward step per launch");
+  int rc;
+  if ((rc = band ? band_ensure(c) : dense_ensure(c))) return rc;
+  if (band) {
+    const BandAdjWork &D = c->band;
+    return direct_adjoint_chunks(c, c->band_nb, D.flag, [&](int phase, int b0, int nb) -> hipError_t {
+      if (phase == 0) { launch_band_assemble(c->S, A, c->W.x64, D, b0, nb, c->stream); c->dense_launches += 2; return hipSuccess; }
+      if (phase == 1) return launch_band_factor(D, nb, c->stream, &c->dense_launches);
+      c->dense_launches += 1;
+      return launch_band_adjoint_step(c->S, c->W, A, D, b0, nb, c->stream);
+    });
+  }
+  const DenseAdjWork &D = c->dense;
+  const int n = 3 * c->host.N;
+  return direct_adjoint_chunks(c, c->dense_nb, D.flag, [&](int phase, int b0, int nb) -> hipError_t {
+    if (phase == 0) { launch_dense_assemble(c->S, A, c->W.x64, D, b0, nb, c->stream); c->dense_launches += 2; }
+    else if (phase == 1) c->dense_launches += launch_dense_factor(D, n, nb, c->stream);
+    else { launch_dense_adjoint_step(c->S, c->W, A, D, b0, nb, c->stream); c->dense_launches += 1; }
+    return hipSuccess;
+  });
 }
 
 // Outcome of a step launcher that was handed a kernel choice (dc_kernelplan.h). The launchers return hipErrorInvalidValue without launching
@@ -415,7 +477,7 @@ int enqueue_pd_step(dc_ctx *c, const FwdArgs &A) {
   return DC_OK;
 }
 int enqueue_adjoint_step(dc_ctx *c, const BwdArgs &A) {
-  if (c->params.adjoint_mode == 2) return enqueue_dense_adjoint(c, A);
+  if (c->params.adjoint_mode == 2 || c->params.adjoint_mode == 3) return enqueue_dense_adjoint(c, A);
   if (!use_cluster_bwd(c)) {
     const AdjChoice ch = adjoint_choice(c->facts, A.mode, A.block_pre != 0, kernel_switches().bwd_threads);
     return launched(c, launch_adjoint_step(c->S, c->W, A, ch, c->B, c->stream), ch.dense ? "adjoint step, explicit inverse" : ch.coarse ? "adjoint step, coarse level" :
@@ -487,7 +549,7 @@ int enqueue_backward_steps(dc_ctx *c, int slot, int nsteps, Seeds seeds, const b
   }
   if (c->S.Af > 0) HIPCHK(c, hipMemsetAsync(dxf_slot(c, first), 0, sizeof(float) * xf_elems(c) * nsteps, c->stream));
   const bool inj_inside = c->inj_slot >= first && c->inj_slot <= slot;
-  const bool fused = fuse_steps_enabled() && nsteps > 1 && !inj_inside && c->params.adjoint_mode != 2;
+  const bool fused = fuse_steps_enabled() && nsteps > 1 && !inj_inside && c->params.adjoint_mode != 2 && c->params.adjoint_mode != 3;
   auto start_of = [&](int s) { return is_start ? *is_start : s == c->start_slot + 1; };
   if (fused) {
     BwdArgs A = bwd_args(c, slot, start_of(slot), seeds);
@@ -518,7 +580,7 @@ int kernel_time_end(dc_ctx *c, bool bwd, int launches) {
   HIPCHK(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
   const int chunks = (bwd ? use_cluster_bwd(c) : use_cluster_fwd(c)) ? (c->B + c->cl.nb - 1) / c->cl.nb : 1;
   (bwd ? c->bwd_ms : c->fwd_ms) += ms;
-  (bwd ? c->bwd_launches : c->fwd_launches) += (bwd && c->params.adjoint_mode == 2) ? c->dense_launches - c->dense_mark : launches * chunks;
+  (bwd ? c->bwd_launches : c->fwd_launches) += (bwd && (c->params.adjoint_mode == 2 || c->params.adjoint_mode == 3)) ? c->dense_launches - c->dense_mark : launches * chunks;
   return cluster_check(c);
 }
 
@@ -579,6 +641,7 @@ int dc_destroy(dc_ctx *c) {
   free_cluster(c);
   free_pool(c->table_allocs);
   free_pool(c->batch_allocs);
+  free_pool(c->band_allocs);
   (void) hipEventDestroy(c->ev_a); (void) hipEventDestroy(c->ev_b);
   (void) hipEventDestroy(c->ev_t0); (void) hipEventDestroy(c->ev_t1);
   for (hipEvent_t e : c->ev_d) if (e) (void) hipEventDestroy(e);
@@ -627,6 +690,7 @@ int dc_set_params(dc_ctx *c, const dc_params *p) {
   if (!c || !p) return DC_ERR_INVALID;
   if (!(p->time_step > 0) || !(p->density > 0)) return fail(c, DC_ERR_INVALID, "dc_set_params: time_step and density must be > 0");
   if (c->mesh_set) { const int rc = check_dense_mode(c, p->adjoint_mode, c->host.N, "dc_set_params"); if (rc) return rc; }
+  if (c->mesh_set && c->built) { const int rc = check_band_mode(c, p->adjoint_mode, c->band_extra, "dc_set_params"); if (rc) return rc; }
   c->params = *p;
   c->built = false;
   return DC_OK;
@@ -690,6 +754,7 @@ int dc_build(dc_ctx *c) {
   const bool defl = plan.defl_rows > 0 && build_deflation_cached(c, H, deflation_want(p), plan.defl_rows, &HD);
   plan.set_deflation(defl, sw);
   c->bandwidth = plan.bandwidth;
+  { const int rc = check_band_mode(c, p.adjoint_mode, c->band_extra, "dc_build"); if (rc) return rc; }
   c->defl_k = HD ? HD->k : 0; c->defl_probe = HD ? HD->probe_iterations : 0;
   DevSystem &S = c->S;
   if (c->host_only) {       // which kernel set this system would get (dc_get_layout): the same plan, nothing uploaded
@@ -816,8 +881,8 @@ int dc_set_solver(dc_ctx *c, double forward_tol, double backward_tol, int gradie
   if (!c) return DC_ERR_INVALID;
   c->params.forward_tol = forward_tol; c->params.backward_tol = backward_tol;
   c->params.gradient_clipping = gradient_clipping; c->params.gradient_clipping_threshold = clip_threshold;
-  // a direct solve is asked for: the dense one (mode 2) is one, so it stays; otherwise the Krylov direct solve (mode 1)
-  c->params.adjoint_mode = force_direct_adjoint ? (c->params.adjoint_mode == 2 ? 2 : 1) : 0;
+  // a direct solve is asked for: the dense one (mode 2) and the banded one (mode 3) are, so they stay; otherwise the Krylov direct solve (mode 1)
+  c->params.adjoint_mode = force_direct_adjoint ? ((c->params.adjoint_mode == 2 || c->params.adjoint_mode == 3) ? c->params.adjoint_mode : 1) : 0;
   return DC_OK;   // solver knobs are kernel arguments: no rebuild, the batch and its tape stay valid
 }
 
@@ -885,7 +950,9 @@ int dc_alloc_batch(dc_ctx *c, int B, int tape) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   free_pool(c->batch_allocs);
+  free_pool(c->band_allocs);
   c->dense = DenseAdjWork{}; c->dense_nb = 0;
+  c->band = BandAdjWork{}; c->band_nb = 0;
   c->B = B; c->tape = tape; c->start_slot = 0;
   const int N = c->host.N, Af = (int) c->host.att_vertex.size(), NC = c->S.NC, G = c->S.ngroups;
   const size_t se = (size_t) B * 3 * N, slots = (size_t) tape + 1;
@@ -1721,6 +1788,24 @@ int dc_get_adjoint_matrix(dc_ctx *c, int slot, int rollout, double *K) {
   const int N = c->host.N, n = 3 * N;
   if ((rc = check_dense_mode(c, 2, N, "dc_get_adjoint_matrix"))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
+  if (c->params.adjoint_mode == 3) {      // the band-assembled K, exact zeros outside the band
+    if ((rc = band_ensure(c))) return rc;
+    const BandAdjWork &D = c->band;
+    launch_band_assemble(c->S, bwd_args(c, slot, false, Seeds::none), c->W.x64, D, rollout, 1, c->stream);
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> Bd((size_t) D.ldab * n);
+    HIPCHK(c, hipMemcpyAsync(Bd.data(), D.AB, Bd.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::fill(K, K + (size_t) n * n, 0.0);
+    for (int col = 0; col < n; col++) {
+      const int uj = c->user_of.empty() ? col / 3 : c->user_of[col / 3];
+      for (int r = std::max(0, col - D.kl); r <= std::min(n - 1, col + D.kl); r++) {
+        const int ui = c->user_of.empty() ? r / 3 : c->user_of[r / 3];
+        K[(size_t) (3 * ui + r % 3) * n + 3 * uj + col % 3] = Bd[(size_t) col * D.ldab + (2 * D.kl + r - col)];
+      }
+    }
+    return DC_OK;
+  }
   if ((rc = dense_ensure(c))) return rc;
   const DenseAdjWork &D = c->dense;
   launch_dense_assemble(c->S, bwd_args(c, slot, false, Seeds::none), c->W.x64, D, rollout, 1, c->stream);
@@ -1739,6 +1824,24 @@ int dc_get_adjoint_matrix(dc_ctx *c, int slot, int rollout, double *K) {
           K[(size_t) (3 * ui + ci) * n + 3 * uj + cj] = col[ci * N + i];
         }
     }
+  return DC_OK;
+}
+
+int dc_set_adjoint_band(dc_ctx *c, int extra_vertices) {
+  if (!c) return DC_ERR_INVALID;
+  if (extra_vertices < 0) return fail(c, DC_ERR_INVALID, "dc_set_adjoint_band: extra_vertices must be >= 0");
+  if (c->built) { const int rc = check_band_mode(c, c->params.adjoint_mode, extra_vertices, "dc_set_adjoint_band"); if (rc) return rc; }
+  c->band_extra = extra_vertices;       // (band_ensure compares the band it allocated with the one now asked for)
+  return DC_OK;
+}
+
+int dc_get_adjoint_band(const dc_ctx *c, int *kl, int *ldab, long long *bytes_per_rollout) {
+  if (!c) return DC_ERR_INVALID;
+  if (!c->built) return DC_ERR_STATE;
+  const BandPlan bp = band_plan(c->host.N, c->bandwidth, c->band_extra);
+  if (kl) *kl = bp.kl;
+  if (ldab) *ldab = bp.ldab;
+  if (bytes_per_rollout) *bytes_per_rollout = bp.bytes;
   return DC_OK;
 }
 

@@ -83,7 +83,15 @@ typedef struct dc_params {
    * matrix and factored by LU with partial pivoting on the device; u comes from forward / back substitution with the factors, refined
    * against the fp64 residual (at most 3 substitutions) to adjoint_rel_tol; a rollout whose factorisation meets a zero or non-finite pivot
    * takes the fp64 BiCGSTAB fall-back. Meshes of at most 768 vertices (dc_set_params / dc_build fail with DC_ERR_INVALID above);
-   * one backward step per launch, one workgroup per rollout. dc_set_solver(force_direct_adjoint = 1) keeps mode 2.            */
+   * one backward step per launch, one workgroup per rollout. dc_set_solver(force_direct_adjoint = 1) keeps mode 2.
+   * 3 = the same solve on K in band storage (opt-in): with the unknowns interleaved (3 i + c, device numbering) K has half-bandwidth
+   * kl = ku = min(3N - 1, 3 (bw + extra) + 2), bw = the matrix bandwidth dc_get_layout reports, extra = dc_set_adjoint_band (default 0).
+   * LU with partial pivoting in LAPACK band storage (ldab = 2 kl + ku + 1 rounded up to 16) costs at most 2 n kl (kl + ku) flops, n = 3N,
+   * against (2/3) n^3 for mode 2, and ldab n doubles. No 768-vertex cap: a mesh is taken when the band of one rollout fits 8 GB and
+   * 3N doubles plus the substitution's block (one column of kl multipliers, at least 32 x 32 doubles) fit the workgroup's LDS; dc_set_params (on a built context), dc_build and
+   * dc_set_adjoint_band fail with DC_ERR_INVALID and a message naming both numbers otherwise. A rollout whose K has a non-zero outside
+   * the band (a self contact between vertices further apart than bw + extra) is flagged and takes the fp64 BiCGSTAB fall-back from
+   * u = 0, as a zero pivot does: never silent (fp64_iters > 0), never a wrong answer. dc_set_solver(force_direct_adjoint = 1) keeps mode 3. */
   int adjoint_mode;
   double adjoint_rel_tol;
   /* direct adjoint solve: 1 (default) = block-Jacobi preconditioner from the 3x3 diagonal blocks of K = P - dP^T itself, rebuilt
@@ -132,7 +140,8 @@ typedef struct dc_bwd_stats {
   int clipped;
   int used_direct;       /* 1 when the direct (Krylov) solve ran; adjoint_iters then counts its iterations too; 2 = the dense direct solve
                             (adjoint_mode 2): refine_cycles = substitutions with the LU factors, adjoint_iters = cg_iters = 0, fp64_iters =
-                            iterations of the fall-back, last_udiff = the fp64 residual |g - K u| / |g| (residual_verified = 1)            */
+                            iterations of the fall-back, last_udiff = the fp64 residual |g - K u| / |g| (residual_verified = 1); 3 = the banded
+                            direct solve (adjoint_mode 3), the other fields as for 2                                                      */
   float last_udiff;      /* mode 0: |u_new - u|_2 / N; direct solve: relative residual |g - K u| / |g| — mixed precision: the TRUE
                             residual evaluated in fp64 (residual_verified = 1), or, when the last fp32 correction solve was accepted
                             without a further fp64 evaluation, an upper bound: its recurrence residual + twice the measured fp32
@@ -419,6 +428,14 @@ int dc_kernel_times(dc_ctx *ctx, float *fwd_ms, int *fwd_launches, float *bwd_ms
  * only when the environment sets DC_DENSE_TIMES=1 (each chunk then synchronises); reset != 0 zeroes them afterwards.            */
 int dc_get_adjoint_matrix(dc_ctx *ctx, int slot, int rollout, double *K /*(3N)^2*/);
 int dc_dense_phase_times(dc_ctx *ctx, float *ms3, int reset);
+/* The banded direct adjoint solve (adjoint_mode 3). Under mode 3 dc_get_adjoint_matrix returns the band-assembled K, expanded with exact
+ * zeros outside the band (same layout, same 768-vertex limit of the getter), and dc_dense_phase_times the mode-3 steps' split.
+ * dc_set_adjoint_band: extra half-bandwidth in vertices for self contacts that couple outside the matrix band; >= 0, default 0; takes effect
+ * at the next backward step (the band scratch is re-allocated).
+ * dc_get_adjoint_band: what mode 3 would use for the built system (works on a host-only context): kl (= ku), ldab, bytes of band storage
+ * per rollout.                                                                                                                          */
+int dc_set_adjoint_band(dc_ctx *ctx, int extra_vertices);
+int dc_get_adjoint_band(const dc_ctx *ctx, int *kl, int *ldab, long long *bytes_per_rollout);
 
 #ifdef __cplusplus
 }
