@@ -65,6 +65,8 @@ EXPORTED_SYMBOLS = [
     "dc_rollout_forward_async", "dc_rollout_backward_async", "dc_set_fixed_point_schedule_dev", "dc_set_force_schedule_dev", "dc_set_seed_schedule_dev",
     "dc_set_gradient_dev", "dc_get_gradient_dev", "dc_get_states_dev", "dc_get_dxfixed_dev", "dc_get_force_schedule_gradients_dev", "dc_set_mu_dev",
     "dc_set_vertex_forces_dev",
+    "dc_set_primitive_offsets", "dc_set_primitive_offset_schedule", "dc_set_primitive_offsets_dev", "dc_set_primitive_offset_schedule_dev",
+    "dc_get_primitive_centers",
 ]
 
 _lib = None
@@ -122,6 +124,7 @@ class Engine:
         self.N = self.T = self.E = self.Af = 0
         self.B = 0
         self.ngroups = 1
+        self.nprims = 0
 
     def close(self):
         if getattr(self, "h", None):
@@ -190,6 +193,7 @@ class Engine:
             if arr[k].group not in groups:
                 groups.append(arr[k].group)
         self.ngroups = max(len(groups), 1)
+        self.nprims = len(prims)
         self._chk(self.lib.dc_set_primitives(self.h, C.c_int(len(prims)), arr))
 
     def build(self):
@@ -246,6 +250,23 @@ class Engine:
         """second per-vertex force term with factor 1 (the constant force field next to a scheduled wind with fall-off)"""
         a = None if f is None else self._vec(f, 3 * self.N)
         self._chk(self.lib.dc_set_vertex_force_field(self.h, _d(a)))
+
+    def set_primitive_offsets(self, d):
+        """d: [B][G][3] offsets of the primitive groups' centres for the NEXT forward steps (dc_set_primitive_offsets: every primitive of group g
+        of rollout b is tested at fp32(center + d[b][g]), the sum in fp64); None restores the built centres"""
+        a = None if d is None else self._vec(d, 3 * self.ngroups)
+        self._chk(self.lib.dc_set_primitive_offsets(self.h, _d(a)))
+
+    def set_primitive_offset_schedule(self, slot0, d):
+        """d: [nsteps][B][G][3]: the step slot0+k -> slot0+k+1 uses d[k] (dc_set_primitive_offset_schedule)"""
+        d = np.ascontiguousarray(np.asarray(d, dtype=np.float64).reshape(-1, self.B, self.ngroups, 3))
+        self._chk(self.lib.dc_set_primitive_offset_schedule(self.h, C.c_int(slot0), C.c_int(d.shape[0]), _d(d)))
+
+    def get_primitive_centers(self, slot):
+        """[B][P][3] absolute centres of the flattened primitives that the step which produced `slot` used (fp32 values, widened)"""
+        out = np.zeros((self.B, self.nprims, 3))
+        self._chk(self.lib.dc_get_primitive_centers(self.h, C.c_int(slot), _d(out)))
+        return out
 
     def get_force_gradient(self):
         """h^2 (I + dr_df)^T u* per vertex of the last backward step (dL_dfext_vec of the reference)."""
@@ -457,6 +478,18 @@ class Engine:
     def set_vertex_forces_dev(self, fv):
         (p,), f = self._tps((fv, self.B * 3 * self.N, 1))
         self._chk(self.lib.dc_set_vertex_forces_dev(self.h, p, C.c_int(f)))
+
+    def set_primitive_offsets_dev(self, d):
+        """dc_set_primitive_offsets from a CUDA tensor [B][G][3] (a non-contiguous view is copied first); None restores the built centres"""
+        self._offsets_dev = d = None if d is None else d.contiguous()      # (kept alive until the next call: the conversion is only enqueued)
+        (p,), f = self._tps((d, self.B * self.ngroups * 3, 1))
+        self._chk(self.lib.dc_set_primitive_offsets_dev(self.h, p, C.c_int(f)))
+
+    def set_primitive_offset_schedule_dev(self, slot0, nsteps, d):
+        """dc_set_primitive_offset_schedule from a CUDA tensor [nsteps][B][G][3] (a non-contiguous view is copied first)"""
+        self._offset_schedule_dev = d = d.contiguous()
+        (p,), f = self._tps((d, self.B * self.ngroups * 3, nsteps))
+        self._chk(self.lib.dc_set_primitive_offset_schedule_dev(self.h, C.c_int(slot0), C.c_int(nsteps), p, C.c_int(f)))
 
     # ---- device-resident schedules (dc_set_*_schedule) ----
     def set_gradient(self, dL_dx, dL_dv):

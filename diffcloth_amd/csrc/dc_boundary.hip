@@ -5,6 +5,7 @@
 // n is a multiple of 4 and the pointers are 16-byte aligned, one vertex otherwise. Indices are `long` throughout.
 #include <cstdint>
 #include "dc_device.h"
+#include "dc_primoffset.h"
 
 namespace dc {
 namespace {
@@ -203,7 +204,29 @@ __global__ __launch_bounds__(kThreads) void k_dfu(const float *__restrict__ dpar
   out[t] = (T) dpar[r * 8 + 4 + (t - r * 3)];
 }
 
+// ---- (d) primitive centres of `rows` = slots x rollouts from per-group offsets d[rows][G][3] (null: none): one lane per (row, flattened
+// primitive), the rule of dc_primoffset.h — fp64 sum of the built centre and the offset of the primitive's group, rounded once
+template <class T>
+__global__ __launch_bounds__(kThreads) void k_prim_centres(const double *__restrict__ built, const int *__restrict__ group_of_prim, const T *__restrict__ d,
+                                                           float *__restrict__ dst, int P, int G, long total) {
+  const long t = (long) blockIdx.x * kThreads + threadIdx.x;
+  if (t >= total) return;
+  const long r = t / P;
+  const int p = (int) (t - r * P);
+  const T *dr = d ? d + (r * G + group_of_prim[p]) * 3 : nullptr;
+#pragma unroll
+  for (int k = 0; k < 3; k++) dst[t * 3 + k] = offset_centre(built[3 * p + k], dr ? (double) dr[k] : 0.0);
+}
+
 }  // namespace
+
+void launch_prim_centres(const double *built, const int *group_of_prim, const void *d, int is_f32, float *dst, long rows, int P, int G, hipStream_t st) {
+  const long total = rows * P;
+  if (total <= 0) return;
+  const dim3 g(blocks_for(total)), b(kThreads);
+  if (is_f32) hipLaunchKernelGGL(k_prim_centres<float>, g, b, 0, st, built, group_of_prim, (const float *) d, dst, P, G, total);
+  else hipLaunchKernelGGL(k_prim_centres<double>, g, b, 0, st, built, group_of_prim, (const double *) d, dst, P, G, total);
+}
 
 void launch_rows_to_planar(const void *src, int is_f32, float *dst, long rows, int n, const int *user_of, hipStream_t st) {
   if (rows <= 0 || n <= 0) return;

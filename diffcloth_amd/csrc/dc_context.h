@@ -70,6 +70,18 @@ struct dc_ctx {
   float *FVS_S = nullptr;           // [(tape+1)][B] factor on fv of that step
   float *SEEDX = nullptr, *SEEDV = nullptr;   // [(tape+1)][B][3][N] loss gradient w.r.t. the state at the slot (allocated on first use)
   std::vector<char> sched_xf, sched_fu, sched_fvs, sched_seed;
+  // movable obstacles (dc_set_primitive_offsets / dc_set_primitive_offset_schedule, dc_primoffset.h): absolute fp32 centres of the P flattened
+  // primitives. Every row of PC is valid at all times — the built centres until something else is written — and the forward kernels always
+  // read the row of the slot their step produces, so a slot says where its obstacle was (dc_get_primitive_centers).
+  float *PC = nullptr;              // [(tape+1)][B][P][3] centres used by the step that produces the slot
+  float *pc_cur = nullptr;          // [B][P][3] centres of the NEXT steps that have no schedule entry
+  const double *pc_built = nullptr; // [P][3] device copy of dc_primitive::center, and of group_of_prim, for the conversion kernel
+  const int *pc_group = nullptr;
+  // which version of pc_cur a row of PC holds: 0 = the built centres, -1 = a schedule entry, > 0 = the pc_cur of that dc_set_primitive_offsets
+  // call; an unscheduled step copies pc_cur into its row only when the two differ (never, while no offsets are set)
+  std::vector<int> pc_row_gen;
+  int pc_gen = 0, pc_gen_last = 0;
+  std::vector<char> sched_pc;
   void *comm = nullptr;             // RCCL communicator of dc_comm_init (ncclComm_t), one rank per context
   int comm_ranks = 0;
   std::vector<void *> sched_pool;

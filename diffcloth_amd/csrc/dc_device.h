@@ -189,6 +189,10 @@ struct FwdArgs {
   size_t slot_self, slot_meta;                  // ... of the self-contact lists and their meta blocks
   // device-resident schedules (dc_set_*_schedule): per-step strides of x_fixed, fu and fv_scale; 0 = the same values in every step
   size_t slot_xfix, slot_fu, slot_fvs;
+  // absolute fp32 centres of the flattened primitives in this step, [B][nprim][3] (dc_set_primitive_offsets / ..._schedule; the built centres
+  // when none are set): a row of the per-slot table, so a fused sweep always steps by slot_pcen = B * nprim * 3
+  const float *pcen;
+  size_t slot_pcen;
 };
 
 struct BwdArgs {
@@ -247,6 +251,8 @@ void launch_seed_gradient(const float *x, const float *target, float *gx, float 
 void launch_rows_to_planar(const void *src, int is_f32, float *dst, long rows, int n, const int *user_of, hipStream_t st);
 void launch_planar_to_rows(const float *src, void *dst, int is_f32, long rows, int n, const int *user_of, hipStream_t st);
 void launch_cast_in(const void *src, int is_f32, float *dst, long total, hipStream_t st);
+// primitive centres of `rows` = slots x rollouts from per-group offsets (dc_primoffset.h: fp64 sum, one rounding); d null = zero offsets
+void launch_prim_centres(const double *built, const int *group_of_prim, const void *d, int is_f32, float *dst, long rows, int P, int G, hipStream_t st);
 void launch_dfu_from_param(const float *dpar, void *out, int is_f32, long rows, hipStream_t st);
 void launch_dfv_scale(const float *ys, const float *fv, void *out, int is_f32, int nslots, int B, int N, double h2, hipStream_t st);
 void launch_dfv(const float *ys, const float *w, void *out, int is_f32, int nslots, int B, int N, const int *user_of, double h2, hipStream_t st);

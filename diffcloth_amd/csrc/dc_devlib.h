@@ -119,9 +119,8 @@ __device__ __forceinline__ f3 dri_dmu(f3 n, f3 d, float mu) {
 }
 
 // Primitive::isInContact family (Sphere Primitive.cpp:221-261, Capsule :570-604, Plane :66-130, Bowl :362-381) for one
-// flattened primitive.
-__device__ __forceinline__ bool prim_in_contact(const DevPrim &p, f3 pos, f3 &normal) {
-  f3 c = mk(p.cx, p.cy, p.cz);
+// flattened primitive, tested at centre c: the step's centre of this rollout (FwdArgs::pcen), not DevPrim::cx/cy/cz.
+__device__ __forceinline__ bool prim_in_contact(const DevPrim &p, f3 c, f3 pos, f3 &normal) {
   f3 q = pos - c;
   if (p.kind == DC_PRIM_SPHERE || p.kind == DC_PRIM_SPHERE_DISCRETIZED) {      // (discretised: the normal is replaced by detect_primitive)
     float dist = sqrtf(dot(q, q)) - p.radius;
@@ -131,7 +130,7 @@ __device__ __forceinline__ bool prim_in_contact(const DevPrim &p, f3 pos, f3 &no
   if (p.kind == DC_PRIM_BOWL) {     // Bowl::isInContact (Primitive.cpp:362-381): inside of the lower half of a shell, eps 0.005
     const float len = sqrtf(dot(q, q));
     normal = q * (-1.0f / len);
-    return (len - p.radius <= 0.005f) && !(pos.y > p.cy) && (len > p.radius - 0.005f);
+    return (len - p.radius <= 0.005f) && !(pos.y > c.y) && (len > p.radius - 0.005f);
   }
   if (p.kind == DC_PRIM_PLANE) {    // Plane::isInContact (Primitive.cpp:66-130): finite rectangle, eps 0.4, thickness 5, edge tol 5e-4
     const f3 ul = mk(p.tx, p.ty, p.tz), ur = mk(p.ux, p.uy, p.uz), lr = ul * -1.0f, ll = ur * -1.0f;
@@ -211,22 +210,28 @@ __device__ __attribute__((noinline)) void sphere_mesh_normal(const DevSystem &S,
 // Children of one LowerLeg share a group and are tested, per sample, in child order (Primitive.cpp:410-418).
 // (not inlined: it runs once per vertex and step, and its plane / capsule branches must not weigh on the register allocation
 // of the PD / PCG loops of the kernels that call it)
-__device__ __attribute__((noinline)) int detect_primitive(const DevSystem &S, f3 pos, f3 vel, f3 &normal) {
+// cen: the absolute fp32 centres [nprim][3] of THIS rollout in THIS step (a row of the table FwdArgs::pcen points into; the built centres
+// when no offsets are set). Every caller of one step passes the same row: the detection that seeds the self-contact layering
+// (dc_selflib.h) and the step kernel must see the same obstacle.
+__device__ __attribute__((noinline)) int detect_primitive(const DevSystem &S, const float *cen, f3 pos, f3 vel, f3 &normal) {
+  const float DC_G *cg = (const float DC_G *) cen;
   int p0 = 0;
   while (p0 < S.nprim) {
     int p1 = p0;
     while (p1 < S.nprim && S.prims[p1].group == S.prims[p0].group) p1++;
     for (int k = 0; k < 3; k++) {
       f3 q = pos + vel * (S.h * 0.5f * (float) k);
-      for (int p = p0; p < p1; p++)
-        if (prim_in_contact(S.prims[p], q, normal)) {
+      for (int p = p0; p < p1; p++) {
+        const f3 c = mk(cg[3 * p], cg[3 * p + 1], cg[3 * p + 2]);
+        if (prim_in_contact(S.prims[p], c, q, normal)) {
           if (S.prims[p].kind == DC_PRIM_SPHERE_DISCRETIZED && S.dsph_ntri > 0) {
             const double ts = S.h64 * (0.5 * (double) k);
-            sphere_mesh_normal(S, S.prims[p], (double) pos.x + (double) vel.x * ts - (double) S.prims[p].cx, (double) pos.y + (double) vel.y * ts - (double) S.prims[p].cy,
-                               (double) pos.z + (double) vel.z * ts - (double) S.prims[p].cz, normal);
+            sphere_mesh_normal(S, S.prims[p], (double) pos.x + (double) vel.x * ts - (double) c.x, (double) pos.y + (double) vel.y * ts - (double) c.y,
+                               (double) pos.z + (double) vel.z * ts - (double) c.z, normal);
           }
           return p;
         }
+      }
     }
     p0 = p1;
   }

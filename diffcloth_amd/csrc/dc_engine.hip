@@ -10,6 +10,7 @@
 #include "dc_clusterplan.h"
 #include "dc_context.h"
 #include "dc_env.h"
+#include "dc_primoffset.h"
 #include "dc_record.h"
 #include "dc_tables.h"
 #include "dc_spheremesh.h"
@@ -66,6 +67,8 @@ size_t xf_elems(const dc_ctx *c) { return (size_t) c->B * 3 * c->S.Af; }
 float *xf_slot(const dc_ctx *c, int slot) { return c->XF + xf_elems(c) * slot; }
 float *dxf_slot(const dc_ctx *c, int slot) { return c->DXF + xf_elems(c) * slot; }
 float *dpar_slot(const dc_ctx *c, int slot) { return c->DPAR + (size_t) c->B * 8 * slot; }
+size_t pc_elems(const dc_ctx *c) { return (size_t) c->B * c->S.nprim * 3; }
+float *pc_slot(const dc_ctx *c, int slot) { return c->PC + pc_elems(c) * slot; }
 float *seedx_slot(const dc_ctx *c, int slot) { return c->SEEDX + slot_elems(c) * slot; }
 float *seedv_slot(const dc_ctx *c, int slot) { return c->SEEDV + slot_elems(c) * slot; }
 SelfRec self_slot(const dc_ctx *c, int slot) {      // self contacts of record `slot`
@@ -141,6 +144,7 @@ FwdArgs fwd_args(dc_ctx *c, int slot) {
   A.x_fixed = c->xf_cur; A.mu = c->mu; A.fu = c->fu_set ? c->fu : nullptr; A.fv = c->fv_set ? c->fv : nullptr;
   A.fv2 = c->fv2_set ? c->fv2 : nullptr;
   A.fv_scale = nullptr; A.slot_xfix = 0; A.slot_fu = 0; A.slot_fvs = 0;
+  A.pcen = pc_slot(c, slot + 1); A.slot_pcen = pc_elems(c);      // (enqueue_forward_steps has brought the rows up to date)
   // scheduled values of this step (dc_set_*_schedule) take precedence over the current ones
   if (c->S.Af > 0 && c->sched_xf[slot + 1]) A.x_fixed = xf_slot(c, slot + 1);
   if (c->sched_fu[slot + 1]) A.fu = c->FU_S + (size_t) c->B * 3 * (slot + 1);
@@ -509,10 +513,10 @@ int enqueue_forward_steps(dc_ctx *c, int slot, int nsteps, bool carry_targets, i
   int rc;
   FwdArgs FA = fwd_args(c, slot);          // fused: points x_fixed / fu / fv_scale at the first step's schedule entries
   if (fused) {      // a schedule (dc_set_*_schedule) has to cover all steps of a fused sweep or none of them
-    int nxf = 0, nfu = 0, nfvs = 0;
-    for (int k = 1; k <= nsteps; k++) { nxf += c->sched_xf[slot + k]; nfu += c->sched_fu[slot + k]; nfvs += c->sched_fvs[slot + k]; }
-    if ((nxf % nsteps) || (nfu % nsteps) || (nfvs % nsteps))
-      return fail(c, DC_ERR_INVALID, "dc_rollout_forward: a fixed-point / force schedule covers only part of the steps " + std::to_string(slot) + " .. " + std::to_string(slot + nsteps));
+    int nxf = 0, nfu = 0, nfvs = 0, npc = 0;
+    for (int k = 1; k <= nsteps; k++) { nxf += c->sched_xf[slot + k]; nfu += c->sched_fu[slot + k]; nfvs += c->sched_fvs[slot + k]; npc += c->sched_pc[slot + k]; }
+    if ((nxf % nsteps) || (nfu % nsteps) || (nfvs % nsteps) || (npc % nsteps))
+      return fail(c, DC_ERR_INVALID, "dc_rollout_forward: a fixed-point / force / primitive-offset schedule covers only part of the steps " + std::to_string(slot) + " .. " + std::to_string(slot + nsteps));
     if (nxf) FA.slot_xfix = xf_elems(c);
     if (nfu) FA.slot_fu = (size_t) c->B * 3;
     if (nfvs && FA.fv_scale) FA.slot_fvs = (size_t) c->B;
@@ -520,6 +524,11 @@ int enqueue_forward_steps(dc_ctx *c, int slot, int nsteps, bool carry_targets, i
   }
   for (int k = 0; k < nsteps; k++) {
     if (has_xf && !c->sched_xf[slot + k + 1]) HIPCHK(c, hipMemcpyAsync(xf_slot(c, slot + k + 1), c->xf_cur, xf_bytes, hipMemcpyDeviceToDevice, c->stream));
+    // the primitive centres of a step without a schedule entry are the current ones; its row already holds them unless offsets were set since
+    if (c->S.nprim > 0 && !c->sched_pc[slot + k + 1] && c->pc_row_gen[slot + k + 1] != c->pc_gen) {
+      HIPCHK(c, hipMemcpyAsync(pc_slot(c, slot + k + 1), c->pc_cur, sizeof(float) * pc_elems(c), hipMemcpyDeviceToDevice, c->stream));
+      c->pc_row_gen[slot + k + 1] = c->pc_gen;
+    }
     if (fused) continue;
     if (k) FA = fwd_args(c, slot + k);
     if (self_on) launch_self_detect(c->S, c->W, FA, c->B, c->stream);
@@ -1011,6 +1020,27 @@ int dc_alloc_batch(dc_ctx *c, int B, int tape) {
   if ((rc = dev_alloc(c, pool, &c->DXF, (size_t) B * 3 * Af * slots))) return rc;
   if ((rc = dev_alloc(c, pool, &c->FU_S, (size_t) B * 3 * slots))) return rc;
   if ((rc = dev_alloc(c, pool, &c->FVS_S, (size_t) B * slots))) return rc;
+  {   // primitive centres: every row and the current set start as the built centres; offsets and their schedule are gone (B or G changed)
+    const int P = c->S.nprim;
+    std::vector<double> built((size_t) 3 * P);
+    for (int k = 0; k < P; k++) for (int d = 0; d < 3; d++) built[3 * (size_t) k + d] = c->prims[k].center[d];
+    double *pb = nullptr;
+    int *pg = nullptr;
+    if ((rc = dev_alloc(c, pool, &pb, built.size()))) return rc;
+    if ((rc = dev_alloc(c, pool, &pg, (size_t) P))) return rc;
+    if (P > 0) {
+      HIPCHK(c, hipMemcpy(pb, built.data(), built.size() * sizeof(double), hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(pg, c->group_of_prim.data(), (size_t) P * sizeof(int), hipMemcpyHostToDevice));
+    }
+    c->pc_built = pb; c->pc_group = pg;
+    if ((rc = dev_alloc(c, pool, &c->PC, (size_t) B * P * 3 * slots))) return rc;
+    if ((rc = dev_alloc(c, pool, &c->pc_cur, (size_t) B * P * 3))) return rc;
+    launch_prim_centres(c->pc_built, c->pc_group, nullptr, 0, c->PC, (long) slots * B, P, c->ngroups, c->stream);
+    launch_prim_centres(c->pc_built, c->pc_group, nullptr, 0, c->pc_cur, (long) B, P, c->ngroups, c->stream);
+    HIPCHK(c, hipGetLastError());
+    c->pc_row_gen.assign(slots + 1, 0); c->sched_pc.assign(slots + 1, 0);
+    c->pc_gen = 0; c->pc_gen_last = 0;
+  }
   c->SEEDX = c->SEEDV = nullptr;
   c->INJ_X = c->INJ_F = c->INJ_N = c->INJ_SN = c->INJ_SD = nullptr; c->inj_slot = -1;
   c->YS = nullptr; c->keep_y = false;
@@ -1497,6 +1527,85 @@ int dc_clear_schedules(dc_ctx *c) {
   if (!c || c->B <= 0) return fail(c, DC_ERR_STATE, "dc_clear_schedules: no batch");
   std::fill(c->sched_xf.begin(), c->sched_xf.end(), 0); std::fill(c->sched_fu.begin(), c->sched_fu.end(), 0);
   std::fill(c->sched_fvs.begin(), c->sched_fvs.end(), 0); std::fill(c->sched_seed.begin(), c->sched_seed.end(), 0);
+  std::fill(c->sched_pc.begin(), c->sched_pc.end(), 0);      // (the rows keep their entries until a step overwrites them: pc_row_gen = -1)
+  return DC_OK;
+}
+
+// ---- movable obstacles: per-rollout, per-step offsets of the primitive groups' centres (dc_primoffset.h holds the rule). The reference reads
+//      Primitive::center at every step (Simulation.cpp:153-191) and exposes it read-write (python_interface.cpp:285) ----
+namespace {
+// the checks the four setters share: a batch on a device context (DC_ERR_STATE otherwise), primitives to move (DC_ERR_INVALID)
+int check_offsets(dc_ctx *c, const char *who, int slot_lo, int slot_hi) {
+  int rc = check_batch(c, slot_lo, slot_hi);
+  if (rc) return rc;
+  if (c->ngroups <= 0 || c->S.nprim <= 0) return fail(c, DC_ERR_INVALID, std::string(who) + ": the context has no primitives");
+  return DC_OK;
+}
+// rows x [G][3] offsets on the host -> rows x [P][3] centres
+void host_centres(const dc_ctx *c, const double *d, long rows, std::vector<float> &out) {
+  const int P = c->S.nprim, G = c->ngroups;
+  std::vector<double> built((size_t) 3 * P);
+  for (int k = 0; k < P; k++) for (int q = 0; q < 3; q++) built[3 * (size_t) k + q] = c->prims[k].center[q];
+  out.resize((size_t) rows * P * 3);
+  for (long r = 0; r < rows; r++) expand_centres(P, built.data(), c->group_of_prim.data(), d ? d + (size_t) r * G * 3 : nullptr, out.data() + (size_t) r * P * 3);
+}
+}  // namespace
+
+int dc_set_primitive_offsets(dc_ctx *c, const double *d) {
+  int rc = check_offsets(c, "dc_set_primitive_offsets", 0, 0);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<float> cen;
+  host_centres(c, d, c->B, cen);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(c->pc_cur, cen.data(), cen.size() * sizeof(float), hipMemcpyHostToDevice));
+  c->pc_gen = d ? ++c->pc_gen_last : 0;
+  return DC_OK;
+}
+
+int dc_set_primitive_offsets_dev(dc_ctx *c, const void *d_d, int is_f32) {
+  int rc = check_offsets(c, "dc_set_primitive_offsets_dev", 0, 0);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  launch_prim_centres(c->pc_built, c->pc_group, d_d, is_f32, c->pc_cur, c->B, c->S.nprim, c->ngroups, c->stream);
+  HIPCHK(c, hipGetLastError());
+  c->pc_gen = d_d ? ++c->pc_gen_last : 0;
+  return DC_OK;
+}
+
+int dc_set_primitive_offset_schedule(dc_ctx *c, int slot0, int nsteps, const double *d) {
+  int rc = check_offsets(c, "dc_set_primitive_offset_schedule", slot0, slot0 + nsteps);
+  if (rc) return rc;
+  if (nsteps < 1 || !d) return fail(c, DC_ERR_INVALID, "dc_set_primitive_offset_schedule: null schedule");
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<float> cen;
+  host_centres(c, d, (long) nsteps * c->B, cen);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(pc_slot(c, slot0 + 1), cen.data(), cen.size() * sizeof(float), hipMemcpyHostToDevice));
+  for (int k = 1; k <= nsteps; k++) { c->sched_pc[slot0 + k] = 1; c->pc_row_gen[slot0 + k] = -1; }
+  return DC_OK;
+}
+
+int dc_set_primitive_offset_schedule_dev(dc_ctx *c, int slot0, int nsteps, const void *d_d, int is_f32) {
+  int rc = check_offsets(c, "dc_set_primitive_offset_schedule_dev", slot0, slot0 + nsteps);
+  if (rc) return rc;
+  if (nsteps < 1 || !d_d) return fail(c, DC_ERR_INVALID, "dc_set_primitive_offset_schedule_dev: null schedule");
+  HIPCHK(c, hipSetDevice(c->device));
+  launch_prim_centres(c->pc_built, c->pc_group, d_d, is_f32, pc_slot(c, slot0 + 1), (long) nsteps * c->B, c->S.nprim, c->ngroups, c->stream);
+  HIPCHK(c, hipGetLastError());
+  for (int k = 1; k <= nsteps; k++) { c->sched_pc[slot0 + k] = 1; c->pc_row_gen[slot0 + k] = -1; }
+  return DC_OK;
+}
+
+int dc_get_primitive_centers(dc_ctx *c, int slot, double *out) {
+  int rc = check_batch(c, slot, slot);
+  if (rc) return rc;
+  if (slot < 1 || !out) return fail(c, DC_ERR_INVALID, "dc_get_primitive_centers: slot 0 has no record");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<float> v(pc_elems(c));
+  if (!v.empty()) HIPCHK(c, hipMemcpy(v.data(), pc_slot(c, slot), v.size() * sizeof(float), hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < v.size(); k++) out[k] = v[k];
   return DC_OK;
 }
 

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_res(const DevSystem *__rest
     part += dot(v0, v0);
     int prim = -1;
     f3 nrm = mk(0, 0, 0);
-    if (S.contact_enabled) prim = detect_primitive(S, ld3(xn, i, N), v0, nrm);
+    if (S.contact_enabled) prim = detect_primitive(S, A.pcen + (size_t) b * 3 * S.nprim, ld3(xn, i, N), v0, nrm);
     rec_prim[i] = prim;
     st3(rec_n, i, N, nrm);
     ncontact += (prim >= 0);

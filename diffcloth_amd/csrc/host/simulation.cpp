@@ -386,6 +386,9 @@ void Simulation::configureDevice() {
       for (const Primitive &q : p.primitives) add(q, {p.center[0] + q.centerInit[0], p.center[1] + q.centerInit[1], p.center[2] + q.centerInit[2]});
     else add(p, p.center);
   }
+  primitiveCenterBuilt.clear();
+  for (const Primitive &p : primitives) primitiveCenterBuilt.push_back(p.center);
+  primitiveOffsetSent.clear();
   dc_params prm;
   dc_default_params(&prm);
   prm.time_step = sceneConfig.timeStep;
@@ -449,6 +452,7 @@ void Simulation::rebuildSystem() {
     check(c, dc_build(c), "dc_build");
   });
   fieldSignature.clear();
+  primitiveOffsetSent.clear();       // (dc_build drops the offsets)
   paramsFwdTol = prm.forward_tol; paramsBwdTol = prm.backward_tol; paramsClip = gradientClipping;
   paramsClipThr = gradientClippingThreshold; paramsDirect = backwardGradientForceDirectSolver;
 }
@@ -464,6 +468,18 @@ void Simulation::pushParams() {
   });
   paramsFwdTol = forwardConvergenceThreshold; paramsBwdTol = backwardConvergenceThreshold; paramsClip = gradientClipping;
   paramsClipThr = gradientClippingThreshold; paramsDirect = backwardGradientForceDirectSolver;
+}
+
+void Simulation::pushPrimitiveOffsets() {
+  const size_t G = std::min(primitives.size(), primitiveCenterBuilt.size());
+  if (G == 0) return;
+  VecXd d(3 * G, 0.0);
+  bool moved = false;
+  for (size_t g = 0; g < G; g++)
+    for (int k = 0; k < 3; k++) { d[3 * g + k] = primitives[g].center[k] - primitiveCenterBuilt[g][k]; moved = moved || d[3 * g + k] != 0.0; }
+  if (primitiveOffsetSent.empty() ? !moved : d == primitiveOffsetSent) return;
+  forEachContext([&](dc_ctx *c) { check(c, dc_set_primitive_offsets(c, moved ? d.data() : nullptr), "dc_set_primitive_offsets"); });
+  primitiveOffsetSent = d;
 }
 
 void Simulation::setWindAncCollision(bool wind_, bool collision, bool selfCollision, bool) {
@@ -484,6 +500,10 @@ void Simulation::resetSystem() {
   r0.stepIdx = 0; r0.deviceSlot = 0; r0.t = 0;
   forwardRecords.push_back(r0);
   fixedPointCur = fixedPointRest;
+  for (Primitive &p : primitives) {      // Primitive::reset (Primitive.h:164-172): the obstacles go back to where the scene put them
+    p.center = p.centerInit;
+    for (Primitive &q : p.primitives) q.center = q.centerInit;
+  }
   forEachContext([&](dc_ctx *c) { check(c, dc_clear_schedules(c), "dc_clear_schedules"); });     // per-slot inputs of an earlier device-resident evaluation
   check(ctx, dc_set_state(ctx, 0, r0.x.data(), r0.v.data()), "dc_set_state");
 }
@@ -633,6 +653,7 @@ void Simulation::step() {
   const auto tStart = std::chrono::steady_clock::now();
   selectSetForStep();
   pushParams();
+  pushPrimitiveOffsets();
   const ForwardInformation &prev = forwardRecords.back();
   ForwardInformation rec;
   rec.t = prev.t + sceneConfig.timeStep;
@@ -851,6 +872,7 @@ bool Simulation::rolloutOnDevice(int nsteps) {
   const bool field = enableConstantForcefield && external_force_field.size() == n3;
   const auto tStart = std::chrono::steady_clock::now();
   pushParams();
+  pushPrimitiveOffsets();            // (the obstacle does not move inside a device-resident rollout: nobody writes Primitive::center between its steps)
   const int slot0 = forwardRecords.back().deviceSlot;
   const size_t first = forwardRecords.size();
   // ---- the per-step inputs of step(): wind factor, fillForces terms, stepFixPoints targets (in order: the twirl is incremental) ----

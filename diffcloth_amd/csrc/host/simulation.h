@@ -294,6 +294,12 @@ class Simulation {
   void initScene();
   void configureDevice();
   void pushParams();
+  // The reference reads Primitive::center at every step (isInContactWithObstacle, Simulation.cpp:153-191) and Python writes it between steps
+  // (python_interface.cpp:285): before a step, the offset of every top-level primitive from the centre the contexts were built with goes to
+  // every context (attachment sets included) whenever it differs from what was last sent (dc_set_primitive_offsets).
+  void pushPrimitiveOffsets();
+  std::vector<Vec3d> primitiveCenterBuilt;     // Primitive::center of the top-level primitives at configureDevice
+  VecXd primitiveOffsetSent;                   // [G][3] as last sent; empty = none sent since the contexts were (re)built
   VecXd fixedPointTargets(double t);
   struct DeviceBackwardStep { VecXd dxf, dmu, fvec; double par[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int converged = 0, iters = 0; };
   // host side of stepBackward (Simulation.cpp:1608-1764): accumulate this step's device outputs onto the carried gradient record

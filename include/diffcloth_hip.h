@@ -327,6 +327,30 @@ int dc_set_force_schedule(dc_ctx *ctx, int slot0, int nsteps, const double *fu /
  * Costs two more tape-sized arrays, allocated on first use. dc_step_backward ignores it (its seeds are its arguments). */
 int dc_set_seed_schedule(dc_ctx *ctx, int slot0, int nslots, const double *dL_dx /*nslots*B*3N*/, const double *dL_dv /*or NULL*/);
 int dc_clear_schedules(dc_ctx *ctx);
+/* ---- movable obstacles: per-rollout, per-step primitive centres. The reference reads Primitive::center at every step (isInContactWithObstacle,
+ * Simulation.cpp:153-191) and exposes it read-write (python_interface.cpp:285): a caller moves an obstacle between steps by writing it.
+ * ONE rule: an OFFSET d[b][g][3] per rollout b and primitive group g (the compacted group index of dc_set_mu, G = num_groups); every flattened
+ * primitive p of group g is tested at
+ *     centre_p = fp32( (double) dc_primitive.center_p + d[b][g] )          (the sum in fp64, rounded once)
+ * so a context built at the moved centre and a context given the offset see the same fp32 centre, bit for bit. The children of a LowerLeg share
+ * a group and move together (center_prim + child->centerInit in the reference). Nothing else of the primitive changes: radius, plane corners and
+ * capsule axis (relative to the centre), mu, rotates, the discretised sphere's mesh (relative to the centre). The obstacle stays static in the
+ * reference's sense (v_out has no translation term); an obstacle velocity is not modelled. The adjoint holds the contact normal of the record
+ * constant, as the reference's does: there is no gradient w.r.t. the centre.
+ * dc_set_primitive_offsets: offsets of the NEXT forward steps, like dc_set_uniform_force (d = B*G*3; NULL restores the built centres).
+ * dc_set_primitive_offset_schedule: the step that advances slot slot0 + s to slot0 + s + 1 uses d[s] (nsteps*B*G*3); the rules of
+ * dc_set_force_schedule hold — an entry stays until it is overwritten, dc_clear_schedules or dc_alloc_batch, the per-step calls honour it, and a
+ * fused sweep needs it on all of its steps or on none (DC_ERR_INVALID otherwise).
+ * The _dev forms take DEVICE pointers (fp32 or fp64) on the context's stream, converted by one launch for all slots, no synchronisation.
+ * dc_get_primitive_centers: the absolute centres of the P flattened primitives (dc_set_primitives order) that the step which produced `slot`
+ * used, B*P*3, the fp32 values widened — on the per-step path as in a sweep: a slot says where its obstacle was. Synchronises.
+ * dc_alloc_batch, dc_set_primitives and dc_build drop offsets and schedule (B or G changed). A host-only context refuses all of these with
+ * DC_ERR_STATE; without primitives (G == 0) the setters fail with DC_ERR_INVALID.                                                              */
+int dc_set_primitive_offsets(dc_ctx *ctx, const double *d /*B*G*3 or NULL*/);
+int dc_set_primitive_offset_schedule(dc_ctx *ctx, int slot0, int nsteps, const double *d /*nsteps*B*G*3*/);
+int dc_set_primitive_offsets_dev(dc_ctx *ctx, const void *d_d /*B*G*3 or NULL*/, int is_f32);
+int dc_set_primitive_offset_schedule_dev(dc_ctx *ctx, int slot0, int nsteps, const void *d_d /*nsteps*B*G*3*/, int is_f32);
+int dc_get_primitive_centers(dc_ctx *ctx, int slot, double *c /*B*P*3*/);
 /* states of nslots consecutive slots in one call: x[k*B*3N ...], v likewise (either may be NULL) */
 int dc_get_states(dc_ctx *ctx, int slot0, int nslots, double *x, double *v);
 /* dL_dxfixed of the steps through records slot0 .. slot0+nslots-1 of the last backward sweep / step (B*3Af each) */
@@ -373,7 +397,9 @@ int dc_set_vertex_forces_dev(dc_ctx *ctx, const void *d_f /*B*3N or NULL*/, int 
  * (Simulation.cpp:3947, :1534: dL_dx of the initial state takes no dL_dv / h term) in dc_rollout_backward. -1: this tape holds a LATER segment of a
  * trajectory — no step of it is the start. With it a trajectory can be run as a chain of fused segments over several contexts (e.g. one context per
  * attachment set, SceneConfiguration::customAttachmentVertexIdx, Simulation.cpp:1053-1068): state handed on with dc_get_state_dev / dc_set_state_dev,
- * the carried gradient on the way back with dc_get_gradient / dc_set_gradient (tests/test_gpu_schedules.py). dc_step_backward takes is_start itself. */
+ * the carried gradient on the way back with dc_get_gradient / dc_set_gradient (tests/test_gpu_schedules.py). dc_step_backward takes is_start itself.
+ * (Each context of such a chain has its own primitive offsets — dc_set_primitive_offsets / dc_set_primitive_offset_schedule — and dc_alloc_batch,
+ * dc_set_primitives and dc_build drop them: the caller sends them to every context of the chain.) */
 int dc_set_trajectory_start(dc_ctx *ctx, int start_slot);
 int dc_get_stats(dc_ctx *ctx, int slot, dc_step_stats *fwd /*B or NULL*/, dc_bwd_stats *bwd /*B or NULL*/);
 int dc_sync(dc_ctx *ctx);
