@@ -67,6 +67,8 @@ EXPORTED_SYMBOLS = [
     "dc_set_vertex_forces_dev",
     "dc_set_primitive_offsets", "dc_set_primitive_offset_schedule", "dc_set_primitive_offsets_dev", "dc_set_primitive_offset_schedule_dev",
     "dc_get_primitive_centers",
+    "dc_set_primitive_velocities", "dc_set_primitive_velocity_schedule", "dc_set_primitive_velocities_dev", "dc_set_primitive_velocity_schedule_dev",
+    "dc_get_primitive_velocities", "dc_get_primitive_velocity_gradients", "dc_get_primitive_velocity_gradients_dev",
 ]
 
 _lib = None
@@ -266,6 +268,29 @@ class Engine:
         """[B][P][3] absolute centres of the flattened primitives that the step which produced `slot` used (fp32 values, widened)"""
         out = np.zeros((self.B, self.nprims, 3))
         self._chk(self.lib.dc_get_primitive_centers(self.h, C.c_int(slot), _d(out)))
+        return out
+
+    def set_primitive_velocities(self, w):
+        """w: [B][G][3] velocities of the primitive groups for the NEXT forward steps (dc_set_primitive_velocities: d = (f - v_rot m) - w m in
+        the friction law, detection samples pos + (vel - w) h k / 2; stored as fp32); None = zeros"""
+        a = None if w is None else self._vec(w, 3 * self.ngroups)
+        self._chk(self.lib.dc_set_primitive_velocities(self.h, _d(a)))
+
+    def set_primitive_velocity_schedule(self, slot0, w):
+        """w: [nsteps][B][G][3]: the step slot0+k -> slot0+k+1 uses w[k] (dc_set_primitive_velocity_schedule)"""
+        w = np.ascontiguousarray(np.asarray(w, dtype=np.float64).reshape(-1, self.B, self.ngroups, 3))
+        self._chk(self.lib.dc_set_primitive_velocity_schedule(self.h, C.c_int(slot0), C.c_int(w.shape[0]), _d(w)))
+
+    def get_primitive_velocities(self, slot):
+        """[B][G][3] velocities that the step which produced `slot` used (fp32 values, widened; zeros when none was ever set)"""
+        out = np.zeros((self.B, self.ngroups, 3))
+        self._chk(self.lib.dc_get_primitive_velocities(self.h, C.c_int(slot), _d(out)))
+        return out
+
+    def get_primitive_velocity_gradients(self, slot0, nslots):
+        """[nslots][B][G][3] dL/dw of the backward steps through records slot0 .. slot0+nslots-1 (dc_get_primitive_velocity_gradients)"""
+        out = np.zeros((nslots, self.B, self.ngroups, 3))
+        self._chk(self.lib.dc_get_primitive_velocity_gradients(self.h, C.c_int(slot0), C.c_int(nslots), _d(out)))
         return out
 
     def get_force_gradient(self):
@@ -490,6 +515,23 @@ class Engine:
         self._offset_schedule_dev = d = d.contiguous()
         (p,), f = self._tps((d, self.B * self.ngroups * 3, nsteps))
         self._chk(self.lib.dc_set_primitive_offset_schedule_dev(self.h, C.c_int(slot0), C.c_int(nsteps), p, C.c_int(f)))
+
+    def set_primitive_velocities_dev(self, w):
+        """dc_set_primitive_velocities from a CUDA tensor [B][G][3] (a non-contiguous view is copied first); None = zeros"""
+        self._velocities_dev = w = None if w is None else w.contiguous()      # (kept alive until the next call: the conversion is only enqueued)
+        (p,), f = self._tps((w, self.B * self.ngroups * 3, 1))
+        self._chk(self.lib.dc_set_primitive_velocities_dev(self.h, p, C.c_int(f)))
+
+    def set_primitive_velocity_schedule_dev(self, slot0, nsteps, w):
+        """dc_set_primitive_velocity_schedule from a CUDA tensor [nsteps][B][G][3] (a non-contiguous view is copied first)"""
+        self._velocity_schedule_dev = w = w.contiguous()
+        (p,), f = self._tps((w, self.B * self.ngroups * 3, nsteps))
+        self._chk(self.lib.dc_set_primitive_velocity_schedule_dev(self.h, C.c_int(slot0), C.c_int(nsteps), p, C.c_int(f)))
+
+    def get_primitive_velocity_gradients_dev(self, slot0, nslots, dw):
+        """dL/dw of the backward steps through records slot0 .. slot0+nslots-1 into a contiguous CUDA tensor [nslots][B][G][3]"""
+        (p,), f = self._tps((dw, self.B * self.ngroups * 3, nslots))
+        self._chk(self.lib.dc_get_primitive_velocity_gradients_dev(self.h, C.c_int(slot0), C.c_int(nslots), p, C.c_int(f)))
 
     # ---- device-resident schedules (dc_set_*_schedule) ----
     def set_gradient(self, dL_dx, dL_dv):

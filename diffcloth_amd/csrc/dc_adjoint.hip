@@ -16,6 +16,9 @@
 //           itself — fp32 correction solves (CG first with the diag(P) preconditioner, block-Jacobi preconditioned BiCGSTAB otherwise or once CG
 //           stalls) of a residual evaluated in fp64, fp64 BiCGSTAB fall-back — to a relative residual <= adjoint_rel_tol.
 #define DC_KERNEL_TU
+#ifdef DC_ADJ_MOVING
+#define DC_ADJ_VELOCITY      // (dc_adjoint64.h; see the note below the includes)
+#endif
 #include <cstdlib>
 #include "dc_devlib.h"
 #include "dc_winlib.h"
@@ -24,7 +27,22 @@
 #include "dc_adjoint64.h"
 #include "dc_launch.h"
 
+// This file is two translation units, like dc_adjoint_cl.hip (see the note there). Compiled as itself, k_adjoint_step knows nothing of obstacle
+// velocities: DC_ADJ_VELOCITY is not defined, so AdjCtx / Adj64 have no velocity members, the contact operator forms d = f - v_rot m alone and
+// finish_gradients64 has no dL/dw block — the kernels of every context that was never given a velocity are compiled from the same text as
+// before the feature, and take the argument block without the table (AdjArgs = BwdArgsStatic). dc_adjoint_moving.hip includes this file with
+// DC_ADJ_MOVING: the same source as k_adjoint_step_moving / launch_adjoint_step_moving, which read the velocity rows and write dL/dw;
+// launch_adjoint_step hands a launch with a table over. (With the pointers tested at run time in ONE set of kernels the headline's backward step
+// measured 3 % slower and the split kernel left its register budget)
+#ifdef DC_ADJ_MOVING
+#define k_adjoint_step k_adjoint_step_moving
+#define launch_adjoint_step launch_adjoint_step_moving
+#endif
+
 namespace dc {
+#ifndef DC_ADJ_MOVING
+hipError_t launch_adjoint_step_moving(const DevSystem &S, const DevWork &W, const BwdArgs &A, const AdjChoice &ch, int B, hipStream_t st);
+#endif
 
 constexpr int kMaxRefine = 6;          // fp32 correction solves of the mixed-precision direct adjoint solve before the fp64 fall-back
 constexpr double kFallbackGain = 1e-4; // the fp64 fall-back aims this far below the caller's relative tolerance (direct-solve semantics)
@@ -103,6 +121,9 @@ __device__ __forceinline__ void krylov_sum2(float a, float b, double *slot, doub
 
 struct AdjCtx {
   const float *xnew, *rec_f, *rec_n, *mu;
+#ifdef DC_ADJ_VELOCITY
+  const float *pvel;            // [ngroups][3] obstacle velocities of the record's step, this rollout (prim_d)
+#endif
   const int *rec_prim;
   float *y, *corner, *lds;
   int lds_floats;               // size of the dynamic LDS region (0 without element windows)
@@ -128,7 +149,7 @@ __device__ __forceinline__ f3 contact_JT(const DevSystem &S, const AdjCtx &C, in
   if (prim < 0) return mk(0, 0, 0);
   const int N = S.N;
   f3 n = ld3(C.rec_n, i, N);
-  f3 d = ld3(C.rec_f, i, N) - prim_vout(S.prims[prim], n) * S.mass[i];
+  f3 d = prim_d(S.prims[prim], n, ld3(C.rec_f, i, N), S.mass[i], DC_ADJ_PVEL(C));
   return dri_dfi_T(n, d, C.mu[S.prims[prim].group], z);
 }
 
@@ -167,7 +188,7 @@ __device__ __forceinline__ void contact_transpose(const DevSystem &S, const AdjC
         const int i = i0 + j * THREADS;
         f3 w = mk(0, 0, 0);
         if (pr[j] >= 0) {
-          f3 d = fq[j] - prim_vout(S.prims[pr[j]], nq[j]) * mq[j];
+          f3 d = prim_d(S.prims[pr[j]], nq[j], fq[j], mq[j], DC_ADJ_PVEL(C));
           w = dri_dfi_T(nq[j], d, C.mu[S.prims[pr[j]].group], zq[j]);
         }
         if (i < N) st3(y, i, N, zq[j] + w);
@@ -675,7 +696,7 @@ __device__ DC_OUTLINED Ret32 cg32_solve(const DevSystem &S, AdjCtx C, Krylov32 V
 
 // BLK: direct solve preconditioned with K's own 3 x 3 diagonal blocks (dc_adjprecond.h) instead of diag(P)^-1
 template <int THREADS, bool WIN, bool DENSE, bool BLK, bool COARSE = false>
-__global__ __launch_bounds__(THREADS) void k_adjoint_step(const DevSystem *__restrict__ Sp, DevWork W, BwdArgs A) {
+__global__ __launch_bounds__(THREADS) void k_adjoint_step(const DevSystem *__restrict__ Sp, DevWork W, AdjArgs A) {
   const DevSystem &S = *Sp;
   extern __shared__ __attribute__((aligned(16))) float dyn_lds[];      // element windows (S.win_lds_bytes)
   __shared__ double red[3 * (THREADS / 64)];
@@ -699,12 +720,18 @@ __global__ __launch_bounds__(THREADS) void k_adjoint_step(const DevSystem *__res
     A.is_start = (A.slot - step == A.start_at) ? 1 : 0;            // isStart: Simulation.cpp:3947
     A.inj_x = A.inj_f = A.inj_n = A.inj_sn = A.inj_sd = nullptr;      // (a record from outside is differentiated by a launch of its own)
     if (A.ys) A.ys -= A.slot_state;
+#ifdef DC_ADJ_VELOCITY
+    A.pvel -= A.slot_pvel; A.d_pvel -= A.slot_pvel;
+#endif
   }
   AdjCtx C;
   C.lds = dyn_lds; C.lds_floats = WIN ? S.win_lds_bytes / 4 : 0;
   C.xnew = A.x_new + off; C.rec_f = A.rec_f + off; C.rec_n = A.rec_n + off;
   C.rec_prim = A.rec_prim + (size_t) b * N;
   C.mu = A.mu + (size_t) b * S.ngroups;
+#ifdef DC_ADJ_VELOCITY
+  C.pvel = A.pvel + (size_t) b * 3 * S.ngroups;      // obstacle velocities of the record's step, this rollout
+#endif
   C.y = W.vbest + off; C.corner = W.corner + (size_t) b * 3 * S.NC;
   C.self = A.self; C.b = b;
   C.nself = (S.contact_enabled && S.self_enabled) ? A.self.meta[(size_t) b * kMetaStride] : 0;
@@ -830,6 +857,9 @@ __global__ __launch_bounds__(THREADS) void k_adjoint_step(const DevSystem *__res
   Adj64 C64;
   C64.xprev = A.x_prev + off; C64.vnew = A.v_new + off;
   C64.xnew = C.xnew; C64.rec_f = C.rec_f; C64.rec_n = C.rec_n; C64.mu = C.mu; C64.rec_prim = C.rec_prim;
+#ifdef DC_ADJ_VELOCITY
+  C64.pvel = C.pvel; C64.d_pvel = A.d_pvel + (size_t) b * 3 * S.ngroups;
+#endif
   C64.self = C.self; C64.nself = C.nself; C64.b = b; C64.lds = dyn_lds; C64.lds_floats = C.lds_floats;
   adj64_inject(C64, A, b, N, S.self_cap);
   Work64 W64;
@@ -1054,6 +1084,9 @@ constexpr bool adj_shape_compiled(const AdjShape &) { return true; }
 // The one instance the adjoint choice names (dc_kernelplan.h: adjoint_choice, made per enqueue from the step's arguments): one walk of
 // kAdjShapes at compile time instantiates every shape's kernels.
 hipError_t launch_adjoint_step(const DevSystem &S, const DevWork &W, const BwdArgs &A, const AdjChoice &ch, int B, hipStream_t st) {
+#ifndef DC_ADJ_MOVING
+  if (A.pvel) return launch_adjoint_step_moving(S, W, A, ch, B, st);      // the context has a velocity table
+#endif
   const bool hit = for_first_index<kAdjShapeCount>([&](auto i) {
     constexpr AdjShape s = kAdjShapes[i];
     if constexpr (!adj_shape_compiled(s)) return false;

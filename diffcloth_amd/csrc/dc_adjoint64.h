@@ -25,7 +25,23 @@
 #define DC_OUTLINED __forceinline__
 #endif
 
+// DC_ADJ_VELOCITY, defined by a translation unit before this header: its kernels read the obstacle-velocity rows (dc_set_primitive_velocities) and
+// write dL/dw. Without it Adj64 has no such members, the contact operator forms d = f - v_rot m alone and finish_gradients64 has no dL/dw block:
+// the text the step kernels of contexts without a velocity table are compiled from (dc_adjoint.hip, dc_adjoint_cl.hip as themselves).
+#ifdef DC_ADJ_VELOCITY
+#define DC_ADJ_PVEL(C) ((C).pvel)
+#else
+#define DC_ADJ_PVEL(C) ((const float *) nullptr)
+#endif
+
 namespace dc {
+
+// the step kernels' by-value arguments: with the velocity table, or the block without it (dc_device.h)
+#ifdef DC_ADJ_VELOCITY
+using AdjArgs = BwdArgs;
+#else
+using AdjArgs = BwdArgsStatic;
+#endif
 
 // The leash of the CG correction solves (dc_adjoint.hip: cg32_solve; the split kernel's CG branch): a solve ends unconverged after this many iterations
 // without a new minimum of |r|, or this many iterations in all — the rest of the step is then BiCGSTAB's.
@@ -58,6 +74,10 @@ struct Work64 {
 // what the fp64 operator reads of the step being differentiated
 struct Adj64 {
   const float *xnew, *rec_f, *rec_n, *mu;
+#ifdef DC_ADJ_VELOCITY
+  const float *pvel;                        // [ngroups][3] obstacle velocities of the record's step, this rollout; null = none set
+  float *d_pvel;                            // [ngroups][3] dL/dw of this step, this rollout (finish_gradients64 writes it); null = none set
+#endif
   const float *xprev, *vnew;                // state the step started from, velocity it ended with (tape slots k - 1 and k)
   const int *rec_prim;
   SelfRec self;
@@ -69,7 +89,7 @@ struct Adj64 {
   // operator then works on these values (cases decided in fp64, as the reference does) instead of on the fp32 tape.
   const double *inj_x, *inj_f, *inj_n, *inj_sn, *inj_sd;
 };
-__device__ __forceinline__ void adj64_inject(Adj64 &C, const BwdArgs &A, int b, int N, int cap) {
+__device__ __forceinline__ void adj64_inject(Adj64 &C, const BwdArgsStatic &A, int b, int N, int cap) {
   const size_t off = (size_t) b * 3 * N, so = (size_t) b * 3 * cap;
   C.inj_x = A.inj_x ? A.inj_x + off : nullptr; C.inj_f = A.inj_f ? A.inj_f + off : nullptr; C.inj_n = A.inj_n ? A.inj_n + off : nullptr;
   C.inj_sn = A.inj_sn ? A.inj_sn + so : nullptr; C.inj_sd = A.inj_sd ? A.inj_sd + so : nullptr;
@@ -190,6 +210,15 @@ __device__ __forceinline__ d3 dri_dmu_dd(d3 n, d3 d, double mu) {
 __device__ __forceinline__ d3 prim_vout_d(const DevPrim &p, d3 n) {
   return p.rotates ? cross(mkd(0, 1, 0), n) * 8.0 : mkd(0, 0, 0);   // Primitive.cpp:254-257
 }
+// prim_d (dc_devlib.h) on a record handed in from outside: d = (f - v_rot m) - w m in fp64, w = (double) fp32(w) as the device stores it
+__device__ __forceinline__ d3 prim_d_d(const DevPrim &p, d3 n, d3 f, double m, const float *wv) {
+  d3 d = f - prim_vout_d(p, n) * m;
+  if (wv) {
+    const float DC_G *w = (const float DC_G *) wv + 3 * p.group;
+    d = d - mkd((double) w[0], (double) w[1], (double) w[2]) * m;
+  }
+  return d;
+}
 // dr/dmu (Simulation::calculatedri_dmu, Simulation.cpp:865-879), case decided in fp32 like above
 __device__ __forceinline__ d3 dri_dmu_d(f3 nf, f3 df, float mu) {
   const float sdf = dot(df, nf);
@@ -209,10 +238,10 @@ __device__ __forceinline__ d3 contact_JT_d(const DevSystem &S, const Adj64 &C, i
   const int N = S.N;
   if (C.inj_f) {
     const d3 n = ld3d(C.inj_n, i, N);
-    return dri_dfi_T_dd(n, ld3d(C.inj_f, i, N) - prim_vout_d(S.prims[prim], n) * S.mass64[i], (double) C.mu[S.prims[prim].group], z);
+    return dri_dfi_T_dd(n, prim_d_d(S.prims[prim], n, ld3d(C.inj_f, i, N), S.mass64[i], DC_ADJ_PVEL(C)), (double) C.mu[S.prims[prim].group], z);
   }
   const f3 n = ld3(C.rec_n, i, N);
-  const f3 d = ld3(C.rec_f, i, N) - prim_vout(S.prims[prim], n) * S.mass[i];     // the fp32 record of the forward pass
+  const f3 d = prim_d(S.prims[prim], n, ld3(C.rec_f, i, N), S.mass[i], DC_ADJ_PVEL(C));     // the fp32 record of the forward pass
   return dri_dfi_T_d(n, d, C.mu[S.prims[prim].group], z);
 }
 
@@ -644,8 +673,10 @@ __device__ DC_OUTLINED Ret64<Team> residual64(const DevSystem &S, Adj64 C, Team 
 //   [3]     density term (:1672-1679, adddr_dd = false)
 //   [4..6]  h^2 * sum_i y_i  (dL_dfext_vec summed, :1702-1764; the host applies the wind chain rule)
 // and y = (I + dr_df)^T u as fp32 in y32 (dc_get_force_gradient reads it). Elements are dealt to the Team's parts in contiguous ranges.
+// With an obstacle-velocity table (C.d_pvel): dL/dw of every primitive group, -h sum m_i (dr_i/dd_i)^T u_i over its contacts, next to dL_dmu and
+// under the same rules (normals and contact set constant). [3] stays without the dr/dd term for a moving obstacle too (adddr_dd = false).
 template <int THREADS, class Team>
-__device__ DC_OUTLINED Ret64<Team> finish_gradients64(const DevSystem &S, Adj64 C, Team tm, Work64 W, BwdArgs A, float *__restrict__ y32) {
+__device__ DC_OUTLINED Ret64<Team> finish_gradients64(const DevSystem &S, Adj64 C, Team tm, Work64 W, AdjArgs A, float *__restrict__ y32) {
   auto ret = [&](int res) { return Ret64<Team>{res, 0, 0.0, tm}; };
   const int N = S.N, tid = threadIdx.x, b = C.b;
   const size_t off = (size_t) b * 3 * N;
@@ -706,10 +737,10 @@ __device__ DC_OUTLINED Ret64<Team> finish_gradients64(const DevSystem &S, Adj64 
       double contrib;
       if (C.inj_f) {
         const d3 n = ld3d(C.inj_n, i, N);
-        contrib = dot(dri_dmu_dd(n, ld3d(C.inj_f, i, N) - prim_vout_d(S.prims[prim], n) * m, (double) C.mu[grp]), ui) * h;
+        contrib = dot(dri_dmu_dd(n, prim_d_d(S.prims[prim], n, ld3d(C.inj_f, i, N), m, DC_ADJ_PVEL(C)), (double) C.mu[grp]), ui) * h;
       } else {
         const f3 n = ld3(C.rec_n, i, N);
-        const f3 d = ld3(C.rec_f, i, N) - prim_vout(S.prims[prim], n) * S.mass[i];
+        const f3 d = prim_d(S.prims[prim], n, ld3(C.rec_f, i, N), S.mass[i], DC_ADJ_PVEL(C));
         contrib = dot(dri_dmu_d(n, d, C.mu[grp]), ui) * h;
       }
 #pragma unroll
@@ -743,6 +774,23 @@ __device__ DC_OUTLINED Ret64<Team> finish_gradients64(const DevSystem &S, Adj64 
         for (int c = 0; c < 3 && k0 + c < S.ngroups; c++) A.d_mu[(size_t) b * S.ngroups + k0 + c] += (float) s3[c];
     }
   }
+#ifdef DC_ADJ_VELOCITY
+  if (C.d_pvel) {
+    // dL/dw[g] = -h sum over the vertices i in contact with group g of m_i (dr_i/dd_i)^T u_i (dd_i/dw = -m_i I; the convention of dL_dmu: normals
+    // and contact set held constant), one pass over the own rows per group — only contexts that were ever given a velocity come here
+    float *dw = C.d_pvel;
+    for (int g = 0; g < S.ngroups; g++) {
+      d3 acc = mkd(0, 0, 0);
+      for (int i = tm.r0() + tid; i < tm.r1(); i += THREADS) {
+        const int prim = C.rec_prim[i];
+        if (prim >= 0 && S.prims[prim].group == g) acc = acc + contact_JT_d(S, C, i, ld3d(W.u, i, N)) * S.mass64[i];
+      }
+      if (!tm.sum3(acc.x, acc.y, acc.z, s3)) return ret(-1);
+      if (writer)
+        for (int c = 0; c < 3; c++) dw[3 * g + c] = (float) (-h * s3[c]);
+    }
+  }
+#endif
   if (A.d_param) {
     float *dp = A.d_param + (size_t) b * 8;
     const double scale[9] = {S.k_stretch64 > 0 ? h2 / S.k_stretch64 : 0.0, S.k_bend64 > 0 ? h2 / S.k_bend64 : 0.0,

@@ -14,6 +14,7 @@
 //              block next to it), each followed by the fp64 residual; at most kBandRefine cycles, then (or for a flagged rollout) bicgstab64.
 // No inter-workgroup communication, no atomics; every loop is bounded by n, kl or ku.
 #define DC_KERNEL_TU
+#define DC_ADJ_VELOCITY      // the direct solves read the obstacle-velocity rows when the context has them (dc_adjoint64.h)
 #include "dc_devlib.h"
 #include "dc_adjprecond.h"
 #include "dc_adjoint64.h"

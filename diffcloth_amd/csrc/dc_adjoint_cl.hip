@@ -10,6 +10,9 @@
 //   * with self contacts (which couple arbitrary vertices) y = (I + dr_df)^T z is formed in global memory instead: own rows by
 //     every part, the layered transposed pass by part 0, fence barriers in between.
 #define DC_KERNEL_TU
+#ifdef DC_ADJ_CL_MOVING
+#define DC_ADJ_VELOCITY      // (dc_adjoint64.h; see the note above the kernel)
+#endif
 #include <cstdlib>
 #include "dc_devlib.h"
 #include "dc_winlib.h"
@@ -107,6 +110,9 @@ namespace {
 
 struct AdjCl {
   const float *xnew, *rec_f, *rec_n, *mu;
+#ifdef DC_ADJ_VELOCITY
+  const float *pvel;            // [ngroups][3] obstacle velocities of the record's step, this rollout (prim_d)
+#endif
   const int *rec_prim;
   BufVec yb;                    // y = (I + dr_df)^T z of the rollout, read across parts: write-through stores, L1-bypassing loads
   float *lds, *hc;              // element-window LDS; halo cache: 3 planes of 2 HB floats
@@ -121,7 +127,7 @@ __device__ __forceinline__ f3 contact_JT_cl(const DevSystem &S, const AdjCl &C, 
   if (prim < 0) return mk(0, 0, 0);
   const int N = S.N;
   f3 n = ld3(C.rec_n, i, N);
-  f3 d = ld3(C.rec_f, i, N) - prim_vout(S.prims[prim], n) * S.mass[i];
+  f3 d = prim_d(S.prims[prim], n, ld3(C.rec_f, i, N), S.mass[i], DC_ADJ_PVEL(C));
   return dri_dfi_T(n, d, C.mu[S.prims[prim].group], z);
 }
 
@@ -186,9 +192,24 @@ __device__ __forceinline__ bool adjoint_operator_cl(const DevSystem &S, const De
 
 }  // namespace
 
+// This file is two translation units. Compiled as itself it holds k_adjoint_step_cl, which knows nothing of obstacle velocities
+// (DC_ADJ_VELOCITY undefined: no velocity members in AdjCl / Adj64, d = f - v_rot m alone, no dL/dw block in finish_gradients64): the kernel of
+// every context that was never given a velocity, compiled from the same text as before the feature. Its register allocation sits close to its
+// budget (tests/test_kernel_resources.py) and moves by tens of spilled registers with any live value added. dc_adjoint_cl_moving.hip includes this
+// file with DC_ADJ_CL_MOVING: the same source as k_adjoint_step_cl_moving, which reads the velocity rows and writes dL/dw;
+// launch_adjoint_step_cluster hands a launch with a table over to it.
+#ifdef DC_ADJ_CL_MOVING
+#define DC_ADJ_CL_KERNEL k_adjoint_step_cl_moving
+#define DC_ADJ_CL_LAUNCH launch_adjoint_step_cluster_moving
+#else
+#define DC_ADJ_CL_KERNEL k_adjoint_step_cl
+#define DC_ADJ_CL_LAUNCH launch_adjoint_step_cluster
+hipError_t launch_adjoint_step_cluster_moving(const DevSystem &S, const DevCluster &CL, const DevWork &W, const BwdArgs &A, const ClAdjChoice &ch, int b0, int nb, hipStream_t st);
+#endif
+
 template <int THREADS, bool BLK, bool COARSE = false>
-__global__ __launch_bounds__(THREADS) void k_adjoint_step_cl(const DevSystem *__restrict__ Sp, const DevCluster *__restrict__ Cp, DevWork W,
-                                                             BwdArgs A, int b0, int nb_real, int hc_off, int tail_off) {
+__global__ __launch_bounds__(THREADS) void DC_ADJ_CL_KERNEL(const DevSystem *__restrict__ Sp, const DevCluster *__restrict__ Cp, DevWork W,
+                                                             AdjArgs A, int b0, int nb_real, int hc_off, int tail_off) {
   const DevSystem &S = *Sp;
   const DevCluster &CL = *Cp;
   constexpr int HPT = (1024 + THREADS - 1) / THREADS;
@@ -222,12 +243,18 @@ __global__ __launch_bounds__(THREADS) void k_adjoint_step_cl(const DevSystem *__
     A.is_start = (A.slot - step == A.start_at) ? 1 : 0;            // isStart: Simulation.cpp:3947
     A.inj_x = A.inj_f = A.inj_n = A.inj_sn = A.inj_sd = nullptr;      // (a record from outside is differentiated by a launch of its own)
     if (A.ys) A.ys -= A.slot_state;
+#ifdef DC_ADJ_VELOCITY
+    A.pvel -= A.slot_pvel; A.d_pvel -= A.slot_pvel;
+#endif
   }
   AdjCl C;
   C.lds = dyn_lds; C.lds_floats = hc_off; C.hc = dyn_lds + hc_off;
   C.xnew = A.x_new + off; C.rec_f = A.rec_f + off; C.rec_n = A.rec_n + off;
   C.rec_prim = A.rec_prim + (size_t) b * N;
   C.mu = A.mu + (size_t) b * S.ngroups;
+#ifdef DC_ADJ_VELOCITY
+  C.pvel = A.pvel + (size_t) b * 3 * S.ngroups;      // obstacle velocities of the record's step, this rollout
+#endif
   C.yb = buf_vec(W.vbest + off, N, X.same_xcd);
   C.self = A.self; C.b = b; C.part = part; C.r0 = r0; C.r1 = r1; C.R = R; C.HB = HB;
   C.w0 = part * CL.wpp; C.w1 = min(CL.nwin, C.w0 + CL.wpp);
@@ -262,6 +289,9 @@ __global__ __launch_bounds__(THREADS) void k_adjoint_step_cl(const DevSystem *__
   Adj64 C64;
   C64.xprev = A.x_prev + off; C64.vnew = A.v_new + off;
   C64.xnew = C.xnew; C64.rec_f = C.rec_f; C64.rec_n = C.rec_n; C64.mu = C.mu; C64.rec_prim = C.rec_prim;
+#ifdef DC_ADJ_VELOCITY
+  C64.pvel = C.pvel; C64.d_pvel = A.d_pvel + (size_t) b * 3 * S.ngroups;
+#endif
   C64.self = C.self; C64.nself = C.nself; C64.b = b; C64.lds = dyn_lds; C64.lds_floats = hc_off;
   adj64_inject(C64, A, b, N, S.self_cap);
   Work64 W64;
@@ -604,12 +634,15 @@ static hipError_t launch_adj_cl_inst(const DevSystem &S, const DevCluster &CL, c
   constexpr int THREADS = DC_ADJ_CL_THREADS;
   const ClAdjointLds l = cl_adjoint_lds(CL.HB, CL.win_lds_bytes);
   if (!l.ok || A.mode != 1) return hipErrorInvalidValue;
-  const hipError_t e = ensure_dynamic_lds<k_adjoint_step_cl<THREADS, BLK, COARSE>>(l.bytes);
+  const hipError_t e = ensure_dynamic_lds<DC_ADJ_CL_KERNEL<THREADS, BLK, COARSE>>(l.bytes);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_adjoint_step_cl<THREADS, BLK, COARSE>), dim3((nb + 7) / 8 * 8 * CL.K), dim3(THREADS), l.bytes, st, S.self_dev, CL.self_dev, W, A, b0, nb, l.hc_off, l.tail_off);
+  hipLaunchKernelGGL((DC_ADJ_CL_KERNEL<THREADS, BLK, COARSE>), dim3((nb + 7) / 8 * 8 * CL.K), dim3(THREADS), l.bytes, st, S.self_dev, CL.self_dev, W, A, b0, nb, l.hc_off, l.tail_off);
   return hipGetLastError();
 }
-hipError_t launch_adjoint_step_cluster(const DevSystem &S, const DevCluster &CL, const DevWork &W, const BwdArgs &A, const ClAdjChoice &ch, int b0, int nb, hipStream_t st) {
+hipError_t DC_ADJ_CL_LAUNCH(const DevSystem &S, const DevCluster &CL, const DevWork &W, const BwdArgs &A, const ClAdjChoice &ch, int b0, int nb, hipStream_t st) {
+#ifndef DC_ADJ_CL_MOVING
+  if (A.pvel) return launch_adjoint_step_cluster_moving(S, CL, W, A, ch, b0, nb, st);      // the context has a velocity table
+#endif
   // (with the coarse level: the fall-back is an instance of its own, dc_adjoint.hip launch_adj_coarse)
   if (ch.coarse) return launch_adj_cl_inst<true, true>(S, CL, W, A, b0, nb, st);
   return ch.blk ? launch_adj_cl_inst<true, false>(S, CL, W, A, b0, nb, st) : launch_adj_cl_inst<false, false>(S, CL, W, A, b0, nb, st);

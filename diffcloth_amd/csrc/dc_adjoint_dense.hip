@@ -13,6 +13,7 @@
 //              with the factors (b in LDS), each followed by the fp64 residual (residual64); at most kDenseRefine cycles, then (or for a
 //              flagged rollout) the fp64 BiCGSTAB fall-back (bicgstab64). Gradients, clipping and statistics as in k_adjoint_step.
 #define DC_KERNEL_TU
+#define DC_ADJ_VELOCITY      // the direct solves read the obstacle-velocity rows when the context has them (dc_adjoint64.h)
 #include "dc_devlib.h"
 #include "dc_adjprecond.h"
 #include "dc_adjoint64.h"

@@ -82,6 +82,13 @@ struct dc_ctx {
   std::vector<int> pc_row_gen;
   int pc_gen = 0, pc_gen_last = 0;
   std::vector<char> sched_pc;
+  // obstacle velocities (dc_set_primitive_velocities / dc_set_primitive_velocity_schedule): fp32, per primitive GROUP. All three arrays are
+  // allocated by the first velocity setter after dc_alloc_batch and zeroed; while PV is null the kernels get null pointers and evaluate the
+  // static contact law. Row `slot` of PV is what the step that produced `slot` used and what the backward step through record `slot` reads.
+  float *PV = nullptr;              // [(tape+1)][B][G][3]
+  float *pv_cur = nullptr;          // [B][G][3] velocities of the NEXT steps that have no schedule entry
+  float *DPV = nullptr;             // [(tape+1)][B][G][3] dL/dw of the backward step through record `slot` (overwritten per step)
+  std::vector<char> sched_pv;
   void *comm = nullptr;             // RCCL communicator of dc_comm_init (ncclComm_t), one rank per context
   int comm_ranks = 0;
   std::vector<void *> sched_pool;

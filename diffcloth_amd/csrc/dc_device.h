@@ -193,9 +193,15 @@ struct FwdArgs {
   // when none are set): a row of the per-slot table, so a fused sweep always steps by slot_pcen = B * nprim * 3
   const float *pcen;
   size_t slot_pcen;
+  // fp32 velocities of the primitive groups in this step, [B][ngroups][3] (dc_set_primitive_velocities / ..._schedule), a row of the per-slot
+  // table stepped by slot_pvel = B * ngroups * 3; NULL until a velocity is set for the first time: the kernels then evaluate the static law
+  const float *pvel;
+  size_t slot_pvel;
 };
 
-struct BwdArgs {
+// (BwdArgsStatic: what the adjoint step kernels of a context WITHOUT an obstacle-velocity table take by value — their argument block, and with it
+// their code objects, do not know the feature; BwdArgs below adds the table and is what the host side and every other kernel pass around)
+struct BwdArgsStatic {
   const float *x_new;           // slot k [B][3][N]
   const float *rec_f, *rec_n;   // record k
   const int *rec_prim;
@@ -229,6 +235,14 @@ struct BwdArgs {
   // the self contacts' normals / d ([B][cap][3]) for the fp64 operator; all null for a record the forward kernels made
   const double *inj_x, *inj_f, *inj_n, *inj_sn, *inj_sd;
   float *ys;                    // y = (I + dr_df)^T u* of the step, kept per tape slot (dc_keep_force_gradients; steps by slot_state) or nullptr
+};
+
+struct BwdArgs : BwdArgsStatic {
+  // obstacle velocities the step that produced record k used, [B][ngroups][3] (row k of the table FwdArgs::pvel points into), and dL/dw of this
+  // step, same shape, overwritten (finish_gradients64); both step by slot_pvel, both null until a velocity is set for the first time
+  const float *pvel;
+  float *d_pvel;
+  size_t slot_pvel;
 };
 
 // The step launchers take the choice of dc_kernelplan.h and launch the one instance it names. They return hipErrorInvalidValue, without

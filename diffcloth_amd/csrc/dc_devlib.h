@@ -213,21 +213,32 @@ __device__ __attribute__((noinline)) void sphere_mesh_normal(const DevSystem &S,
 // cen: the absolute fp32 centres [nprim][3] of THIS rollout in THIS step (a row of the table FwdArgs::pcen points into; the built centres
 // when no offsets are set). Every caller of one step passes the same row: the detection that seeds the self-contact layering
 // (dc_selflib.h) and the step kernel must see the same obstacle.
-__device__ __attribute__((noinline)) int detect_primitive(const DevSystem &S, const float *cen, f3 pos, f3 vel, f3 &normal) {
+// wv: the velocities [ngroups][3] of THIS rollout's primitive groups in THIS step (a row of the table FwdArgs::pvel points into), or null
+// when no velocity was ever set. cen is the obstacle's position at the START of the step and the obstacle moves by w h during it: the
+// samples of group g are pos + (vel - w[g]) h k / 2, the look-ahead in the obstacle's frame (w = +0 gives vel - 0 = vel bit for bit).
+// Like cen, every caller of one step passes the same row.
+__device__ __attribute__((noinline)) int detect_primitive(const DevSystem &S, const float *cen, const float *wv, f3 pos, f3 vel, f3 &normal) {
   const float DC_G *cg = (const float DC_G *) cen;
+  const float DC_G *wg = (const float DC_G *) wv;
   int p0 = 0;
   while (p0 < S.nprim) {
     int p1 = p0;
     while (p1 < S.nprim && S.prims[p1].group == S.prims[p0].group) p1++;
+    f3 w = mk(0, 0, 0);
+    if (wv) { const int g = S.prims[p0].group; w = mk(wg[3 * g], wg[3 * g + 1], wg[3 * g + 2]); }
+    const f3 vr = wv ? vel - w : vel;
     for (int k = 0; k < 3; k++) {
-      f3 q = pos + vel * (S.h * 0.5f * (float) k);
+      f3 q = pos + vr * (S.h * 0.5f * (float) k);
       for (int p = p0; p < p1; p++) {
         const f3 c = mk(cg[3 * p], cg[3 * p + 1], cg[3 * p + 2]);
         if (prim_in_contact(S.prims[p], c, q, normal)) {
           if (S.prims[p].kind == DC_PRIM_SPHERE_DISCRETIZED && S.dsph_ntri > 0) {
             const double ts = S.h64 * (0.5 * (double) k);
-            sphere_mesh_normal(S, S.prims[p], (double) pos.x + (double) vel.x * ts - (double) c.x, (double) pos.y + (double) vel.y * ts - (double) c.y,
-                               (double) pos.z + (double) vel.z * ts - (double) c.z, normal);
+            // (the sample point re-formed in fp64 from its fp32 terms, the relative velocity vel - w among them)
+            const double vx = wv ? (double) vel.x - (double) w.x : (double) vel.x, vy = wv ? (double) vel.y - (double) w.y : (double) vel.y;
+            const double vz = wv ? (double) vel.z - (double) w.z : (double) vel.z;
+            sphere_mesh_normal(S, S.prims[p], (double) pos.x + vx * ts - (double) c.x, (double) pos.y + vy * ts - (double) c.y,
+                               (double) pos.z + vz * ts - (double) c.z, normal);
           }
           return p;
         }
@@ -239,6 +250,17 @@ __device__ __attribute__((noinline)) int detect_primitive(const DevSystem &S, co
 }
 __device__ __forceinline__ f3 prim_vout(const DevPrim &p, f3 n) {
   return p.rotates ? cross(mk(0, 1, 0), n) * 8.0f : mk(0, 0, 0);   // Primitive.cpp:254-257, static primitives
+}
+// d of the friction law for a vertex in contact with primitive p: the relative momentum f - m v_out, v_out = v_rot + w (Primitive.cpp's
+// `v_out = this->velocity` plus the rotating sphere's spin). wv: this rollout's [ngroups][3] velocities of the step (dc_set_primitive_velocities),
+// null while none was ever set: then today's expression alone. Evaluated as (f - v_rot m) - w m, so that w = +0 changes no bit.
+__device__ __forceinline__ f3 prim_d(const DevPrim &p, f3 n, f3 f, float m, const float *wv) {
+  f3 d = f - prim_vout(p, n) * m;
+  if (wv) {
+    const float DC_G *w = (const float DC_G *) wv + 3 * p.group;
+    d = d - mk(w[0], w[1], w[2]) * m;
+  }
+  return d;
 }
 
 // ---------------------------------------------------------------------------------------------------

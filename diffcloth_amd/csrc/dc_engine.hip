@@ -69,6 +69,9 @@ float *dxf_slot(const dc_ctx *c, int slot) { return c->DXF + xf_elems(c) * slot;
 float *dpar_slot(const dc_ctx *c, int slot) { return c->DPAR + (size_t) c->B * 8 * slot; }
 size_t pc_elems(const dc_ctx *c) { return (size_t) c->B * c->S.nprim * 3; }
 float *pc_slot(const dc_ctx *c, int slot) { return c->PC + pc_elems(c) * slot; }
+size_t pv_elems(const dc_ctx *c) { return (size_t) c->B * c->ngroups * 3; }
+float *pv_slot(const dc_ctx *c, int slot) { return c->PV + pv_elems(c) * slot; }
+float *dpv_slot(const dc_ctx *c, int slot) { return c->DPV + pv_elems(c) * slot; }
 float *seedx_slot(const dc_ctx *c, int slot) { return c->SEEDX + slot_elems(c) * slot; }
 float *seedv_slot(const dc_ctx *c, int slot) { return c->SEEDV + slot_elems(c) * slot; }
 SelfRec self_slot(const dc_ctx *c, int slot) {      // self contacts of record `slot`
@@ -145,6 +148,7 @@ FwdArgs fwd_args(dc_ctx *c, int slot) {
   A.fv2 = c->fv2_set ? c->fv2 : nullptr;
   A.fv_scale = nullptr; A.slot_xfix = 0; A.slot_fu = 0; A.slot_fvs = 0;
   A.pcen = pc_slot(c, slot + 1); A.slot_pcen = pc_elems(c);      // (enqueue_forward_steps has brought the rows up to date)
+  A.pvel = c->PV ? pv_slot(c, slot + 1) : nullptr; A.slot_pvel = c->PV ? pv_elems(c) : 0;      // (likewise; null = no velocity was ever set)
   // scheduled values of this step (dc_set_*_schedule) take precedence over the current ones
   if (c->S.Af > 0 && c->sched_xf[slot + 1]) A.x_fixed = xf_slot(c, slot + 1);
   if (c->sched_fu[slot + 1]) A.fu = c->FU_S + (size_t) c->B * 3 * (slot + 1);
@@ -202,6 +206,7 @@ BwdArgs bwd_args(dc_ctx *c, int slot, bool is_start, Seeds seeds) {
   A.inj_x = inj ? c->INJ_X : nullptr; A.inj_f = inj ? c->INJ_F : nullptr; A.inj_n = inj ? c->INJ_N : nullptr;
   A.inj_sn = inj ? c->INJ_SN : nullptr; A.inj_sd = inj ? c->INJ_SD : nullptr;
   A.ys = (c->keep_y && c->YS) ? c->YS + se * slot : nullptr;
+  A.pvel = c->PV ? pv_slot(c, slot) : nullptr; A.d_pvel = c->PV ? dpv_slot(c, slot) : nullptr; A.slot_pvel = c->PV ? pv_elems(c) : 0;
   A.slot_state = se; A.slot_prim = sp; A.slot_self = (size_t) c->B * c->self_cap; A.slot_meta = (size_t) c->B * kMetaStride;
   A.slot_param = (size_t) c->B * 8; A.slot_xf = xf_elems(c); A.slot_stats = (size_t) c->B;
   return A;
@@ -513,10 +518,10 @@ int enqueue_forward_steps(dc_ctx *c, int slot, int nsteps, bool carry_targets, i
   int rc;
   FwdArgs FA = fwd_args(c, slot);          // fused: points x_fixed / fu / fv_scale at the first step's schedule entries
   if (fused) {      // a schedule (dc_set_*_schedule) has to cover all steps of a fused sweep or none of them
-    int nxf = 0, nfu = 0, nfvs = 0, npc = 0;
-    for (int k = 1; k <= nsteps; k++) { nxf += c->sched_xf[slot + k]; nfu += c->sched_fu[slot + k]; nfvs += c->sched_fvs[slot + k]; npc += c->sched_pc[slot + k]; }
-    if ((nxf % nsteps) || (nfu % nsteps) || (nfvs % nsteps) || (npc % nsteps))
-      return fail(c, DC_ERR_INVALID, "dc_rollout_forward: a fixed-point / force / primitive-offset schedule covers only part of the steps " + std::to_string(slot) + " .. " + std::to_string(slot + nsteps));
+    int nxf = 0, nfu = 0, nfvs = 0, npc = 0, npv = 0;
+    for (int k = 1; k <= nsteps; k++) { nxf += c->sched_xf[slot + k]; nfu += c->sched_fu[slot + k]; nfvs += c->sched_fvs[slot + k]; npc += c->sched_pc[slot + k]; npv += c->sched_pv[slot + k]; }
+    if ((nxf % nsteps) || (nfu % nsteps) || (nfvs % nsteps) || (npc % nsteps) || (npv % nsteps))
+      return fail(c, DC_ERR_INVALID, "dc_rollout_forward: a fixed-point / force / primitive-offset / primitive-velocity schedule covers only part of the steps " + std::to_string(slot) + " .. " + std::to_string(slot + nsteps));
     if (nxf) FA.slot_xfix = xf_elems(c);
     if (nfu) FA.slot_fu = (size_t) c->B * 3;
     if (nfvs && FA.fv_scale) FA.slot_fvs = (size_t) c->B;
@@ -529,6 +534,8 @@ int enqueue_forward_steps(dc_ctx *c, int slot, int nsteps, bool carry_targets, i
       HIPCHK(c, hipMemcpyAsync(pc_slot(c, slot + k + 1), c->pc_cur, sizeof(float) * pc_elems(c), hipMemcpyDeviceToDevice, c->stream));
       c->pc_row_gen[slot + k + 1] = c->pc_gen;
     }
+    // likewise the obstacle velocities, once a context has them: the row of an unscheduled step takes the current set
+    if (c->PV && !c->sched_pv[slot + k + 1]) HIPCHK(c, hipMemcpyAsync(pv_slot(c, slot + k + 1), c->pv_cur, sizeof(float) * pv_elems(c), hipMemcpyDeviceToDevice, c->stream));
     if (fused) continue;
     if (k) FA = fwd_args(c, slot + k);
     if (self_on) launch_self_detect(c->S, c->W, FA, c->B, c->stream);
@@ -1041,6 +1048,7 @@ int dc_alloc_batch(dc_ctx *c, int B, int tape) {
     c->pc_row_gen.assign(slots + 1, 0); c->sched_pc.assign(slots + 1, 0);
     c->pc_gen = 0; c->pc_gen_last = 0;
   }
+  c->PV = c->pv_cur = c->DPV = nullptr; c->sched_pv.assign(slots + 1, 0);      // obstacle velocities: allocated by their first setter
   c->SEEDX = c->SEEDV = nullptr;
   c->INJ_X = c->INJ_F = c->INJ_N = c->INJ_SN = c->INJ_SD = nullptr; c->inj_slot = -1;
   c->YS = nullptr; c->keep_y = false;
@@ -1528,6 +1536,7 @@ int dc_clear_schedules(dc_ctx *c) {
   std::fill(c->sched_xf.begin(), c->sched_xf.end(), 0); std::fill(c->sched_fu.begin(), c->sched_fu.end(), 0);
   std::fill(c->sched_fvs.begin(), c->sched_fvs.end(), 0); std::fill(c->sched_seed.begin(), c->sched_seed.end(), 0);
   std::fill(c->sched_pc.begin(), c->sched_pc.end(), 0);      // (the rows keep their entries until a step overwrites them: pc_row_gen = -1)
+  std::fill(c->sched_pv.begin(), c->sched_pv.end(), 0);
   return DC_OK;
 }
 
@@ -1606,6 +1615,115 @@ int dc_get_primitive_centers(dc_ctx *c, int slot, double *out) {
   std::vector<float> v(pc_elems(c));
   if (!v.empty()) HIPCHK(c, hipMemcpy(v.data(), pc_slot(c, slot), v.size() * sizeof(float), hipMemcpyDeviceToHost));
   for (size_t k = 0; k < v.size(); k++) out[k] = v[k];
+  return DC_OK;
+}
+
+// ---- moving obstacles: a velocity w[b][g] per rollout and primitive group, per step (include/diffcloth_hip.h holds the rule). The reference
+//      carries the quantity (v_out = this->velocity in every isInContact of Primitive.cpp) and never sets it ----
+namespace {
+// The velocity table, its current set and the gradient table come with the first setter after dc_alloc_batch, all zero: a context that never
+// calls one hands null pointers to its kernels.
+int ensure_velocities(dc_ctx *c) {
+  if (c->PV) return DC_OK;
+  const size_t per = pv_elems(c), slots = (size_t) c->tape + 1;
+  float *pv = nullptr, *cur = nullptr, *dpv = nullptr;
+  int rc;
+  if ((rc = dev_alloc(c, c->batch_allocs, &pv, per * slots))) return rc;
+  if ((rc = dev_alloc(c, c->batch_allocs, &cur, per))) return rc;
+  if ((rc = dev_alloc(c, c->batch_allocs, &dpv, per * slots))) return rc;
+  HIPCHK(c, hipMemsetAsync(pv, 0, sizeof(float) * per * slots, c->stream));
+  HIPCHK(c, hipMemsetAsync(cur, 0, sizeof(float) * per, c->stream));
+  HIPCHK(c, hipMemsetAsync(dpv, 0, sizeof(float) * per * slots, c->stream));
+  c->PV = pv; c->pv_cur = cur; c->DPV = dpv;      // (steps enqueued from here on see the table; those already enqueued ran the static law)
+  return DC_OK;
+}
+// host values -> fp32 in `dst` (n floats); null = zeros. Synchronises, like the host forms of the offsets.
+int upload_velocities(dc_ctx *c, const double *w, float *dst, size_t n) {
+  std::vector<float> v(n, 0.0f);
+  if (w) for (size_t k = 0; k < n; k++) v[k] = (float) w[k];
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(dst, v.data(), n * sizeof(float), hipMemcpyHostToDevice));
+  return DC_OK;
+}
+}  // namespace
+
+int dc_set_primitive_velocities(dc_ctx *c, const double *w) {
+  int rc = check_offsets(c, "dc_set_primitive_velocities", 0, 0);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = ensure_velocities(c))) return rc;
+  return upload_velocities(c, w, c->pv_cur, pv_elems(c));
+}
+
+int dc_set_primitive_velocities_dev(dc_ctx *c, const void *d_w, int is_f32) {
+  int rc = check_offsets(c, "dc_set_primitive_velocities_dev", 0, 0);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = ensure_velocities(c))) return rc;
+  if (d_w) launch_cast_in(d_w, is_f32, c->pv_cur, (long) pv_elems(c), c->stream);
+  else HIPCHK(c, hipMemsetAsync(c->pv_cur, 0, sizeof(float) * pv_elems(c), c->stream));
+  HIPCHK(c, hipGetLastError());
+  return DC_OK;
+}
+
+int dc_set_primitive_velocity_schedule(dc_ctx *c, int slot0, int nsteps, const double *w) {
+  int rc = check_offsets(c, "dc_set_primitive_velocity_schedule", slot0, slot0 + nsteps);
+  if (rc) return rc;
+  if (nsteps < 1 || !w) return fail(c, DC_ERR_INVALID, "dc_set_primitive_velocity_schedule: null schedule");
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = ensure_velocities(c))) return rc;
+  if ((rc = upload_velocities(c, w, pv_slot(c, slot0 + 1), pv_elems(c) * nsteps))) return rc;
+  for (int k = 1; k <= nsteps; k++) c->sched_pv[slot0 + k] = 1;
+  return DC_OK;
+}
+
+int dc_set_primitive_velocity_schedule_dev(dc_ctx *c, int slot0, int nsteps, const void *d_w, int is_f32) {
+  int rc = check_offsets(c, "dc_set_primitive_velocity_schedule_dev", slot0, slot0 + nsteps);
+  if (rc) return rc;
+  if (nsteps < 1 || !d_w) return fail(c, DC_ERR_INVALID, "dc_set_primitive_velocity_schedule_dev: null schedule");
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = ensure_velocities(c))) return rc;
+  launch_cast_in(d_w, is_f32, pv_slot(c, slot0 + 1), (long) (pv_elems(c) * nsteps), c->stream);      // one launch for all slots
+  HIPCHK(c, hipGetLastError());
+  for (int k = 1; k <= nsteps; k++) c->sched_pv[slot0 + k] = 1;
+  return DC_OK;
+}
+
+int dc_get_primitive_velocities(dc_ctx *c, int slot, double *w) {
+  int rc = check_batch(c, slot, slot);
+  if (rc) return rc;
+  if (slot < 1 || !w) return fail(c, DC_ERR_INVALID, "dc_get_primitive_velocities: slot 0 has no record");
+  std::vector<float> v(pv_elems(c), 0.0f);      // (no velocity was ever set: the step used none)
+  if (c->PV && !v.empty()) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(v.data(), pv_slot(c, slot), v.size() * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  for (size_t k = 0; k < v.size(); k++) w[k] = v[k];
+  return DC_OK;
+}
+
+int dc_get_primitive_velocity_gradients(dc_ctx *c, int slot0, int nslots, double *dL_dw) {
+  int rc = check_batch(c, slot0, slot0 + nslots - 1);
+  if (rc) return rc;
+  if (slot0 < 1 || nslots < 1 || !dL_dw) return fail(c, DC_ERR_INVALID, "dc_get_primitive_velocity_gradients: slot 0 has no record");
+  if (!c->PV) return fail(c, DC_ERR_STATE, "dc_get_primitive_velocity_gradients: no primitive velocity has been set on this batch");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<float> v(pv_elems(c) * nslots);
+  HIPCHK(c, hipMemcpy(v.data(), dpv_slot(c, slot0), v.size() * sizeof(float), hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < v.size(); k++) dL_dw[k] = v[k];
+  return DC_OK;
+}
+
+int dc_get_primitive_velocity_gradients_dev(dc_ctx *c, int slot0, int nslots, void *d_dL_dw, int is_f32) {
+  int rc = check_batch(c, slot0, slot0 + nslots - 1);
+  if (rc) return rc;
+  if (slot0 < 1 || nslots < 1 || !d_dL_dw) return fail(c, DC_ERR_INVALID, "dc_get_primitive_velocity_gradients_dev: slot 0 has no record");
+  if (!c->PV) return fail(c, DC_ERR_STATE, "dc_get_primitive_velocity_gradients_dev: no primitive velocity has been set on this batch");
+  HIPCHK(c, hipSetDevice(c->device));
+  launch_copy_cast(dpv_slot(c, slot0), d_dL_dw, is_f32, (long) (pv_elems(c) * nslots), c->stream);
+  HIPCHK(c, hipGetLastError());
   return DC_OK;
 }
 

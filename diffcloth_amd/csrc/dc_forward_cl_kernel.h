@@ -155,6 +155,8 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_cl(const DevSystem *__restr
   const float *fu_s = A.fu ? A.fu + (size_t) step * A.slot_fu : nullptr;
   const float *fvs_s = A.fv_scale ? A.fv_scale + (size_t) step * A.slot_fvs : nullptr;
   const float *pcen_s = A.pcen + (size_t) step * A.slot_pcen;      // this step's primitive centres, all rollouts
+  const float *pvel_s = A.pvel ? A.pvel + (size_t) step * A.slot_pvel + (size_t) b * 3 * S.ngroups : nullptr;      // this step's obstacle velocities of this rollout (null: none set)
+  const float *pvel_all = A.pvel ? A.pvel + (size_t) step * A.slot_pvel : nullptr;
   // the tape state and f / r are read across parts: write-through stores, L1-bypassing loads (xnb, vinb, rfb, rrb, xob, vob)
   const BufVec xnb = buf_vec(A.x_in + off + so, N, X.same_xcd), vinb = buf_vec(A.v_in + off + so, N, X.same_xcd);
   const BufVec rfb = buf_vec(A.rec_f + off + so, N, X.same_xcd), rrb = buf_vec(A.rec_r + off + so, N, X.same_xcd);
@@ -166,7 +168,7 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_cl(const DevSystem *__restr
   if constexpr (DETECT) {                     // detection + layering of this step: part 0, then the lists change hands
     X.site = 2;
     if (part == 0) {
-      self_detect_rollout<THREADS>(S, W, b, A.x_in + so, A.v_in + so, A.rec_prim + (size_t) step * A.slot_prim, srec, fu_s, A.fv, fvs_s, pcen_s, (int *) lds, A.fv2);
+      self_detect_rollout<THREADS>(S, W, b, A.x_in + so, A.v_in + so, A.rec_prim + (size_t) step * A.slot_prim, srec, fu_s, A.fv, fvs_s, pcen_s, pvel_all, (int *) lds, A.fv2);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the lists have left the CU before the exchange below tells the other parts they exist
       __syncthreads();
     }
@@ -202,7 +204,7 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_cl(const DevSystem *__restr
     part_s += dot(v0, v0);
     int prim = -1;
     f3 nrm = mk(0, 0, 0);
-    if (S.contact_enabled) prim = detect_primitive(S, pcen_s + (size_t) b * 3 * S.nprim, ld3c(xnb, i), v0, nrm);
+    if (S.contact_enabled) prim = detect_primitive(S, pcen_s + (size_t) b * 3 * S.nprim, pvel_s, ld3c(xnb, i), v0, nrm);
     rec_prim[i] = prim;
     st3(rec_n, i, N, nrm);
     ncontact += (prim >= 0);
@@ -233,7 +235,7 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_cl(const DevSystem *__restr
       const int prim = rec_prim[i];
       if (prim >= 0) {  // calculateDryFrictionVector, primitive part (Simulation.cpp:640-652)
         f3 n = ld3(rec_n, i, N);
-        f3 d = f - prim_vout(S.prims[prim], n) * m;
+        f3 d = prim_d(S.prims[prim], n, f, m, pvel_s);
         r = dry_friction(n, d, mu[S.prims[prim].group]);
       }
       st3c(rfb, i, f);

@@ -81,11 +81,13 @@ __device__ __forceinline__ void pd_step_pk(const DevSystem *__restrict__ Sp, con
   const float *fu_s = A.fu ? A.fu + (size_t) step * A.slot_fu : nullptr;
   const float *fvs_s = A.fv_scale ? A.fv_scale + (size_t) step * A.slot_fvs : nullptr;
   const float *pcen_s = A.pcen + (size_t) step * A.slot_pcen;      // this step's primitive centres, all rollouts
+  const float *pvel_s = A.pvel ? A.pvel + (size_t) step * A.slot_pvel + (size_t) b * 3 * S.ngroups : nullptr;      // this step's obstacle velocities of this rollout (null: none set)
+  const float *pvel_all = A.pvel ? A.pvel + (size_t) step * A.slot_pvel : nullptr;
   SelfRec srec = A.self;                      // self contacts of this step's record
   srec.pair += (size_t) step * A.slot_self; srec.nrm += (size_t) step * A.slot_self; srec.dvec += (size_t) step * A.slot_self;
   srec.meta += (size_t) step * A.slot_meta; srec.verts += (size_t) step * 2 * A.slot_self;
   if constexpr (DETECT) {                     // fused sweeps: detection + layering of this step run here (dc_selflib.h)
-    self_detect_rollout<THREADS>(S, W, b, A.x_in + so, A.v_in + so, A.rec_prim + (size_t) step * A.slot_prim, srec, fu_s, A.fv, fvs_s, pcen_s, (int *) lp, A.fv2);
+    self_detect_rollout<THREADS>(S, W, b, A.x_in + so, A.v_in + so, A.rec_prim + (size_t) step * A.slot_prim, srec, fu_s, A.fv, fvs_s, pcen_s, pvel_all, (int *) lp, A.fv2);
     __syncthreads();
   }
   const float *mu = A.mu + (size_t) b * S.ngroups;
@@ -124,7 +126,7 @@ __device__ __forceinline__ void pd_step_pk(const DevSystem *__restrict__ Sp, con
     part += dot(v0, v0);
     int prim = -1;
     f3 nrm = mk(0, 0, 0);
-    if (S.contact_enabled) prim = detect_primitive(S, pcen_s + (size_t) b * 3 * S.nprim, ld3(xn, i, N), v0, nrm);
+    if (S.contact_enabled) prim = detect_primitive(S, pcen_s + (size_t) b * 3 * S.nprim, pvel_s, ld3(xn, i, N), v0, nrm);
     rec_prim[i] = prim;
     st3(rec_n, i, N, nrm);
     ncontact += (prim >= 0);
@@ -157,7 +159,7 @@ __device__ __forceinline__ void pd_step_pk(const DevSystem *__restrict__ Sp, con
       const int prim = rec_prim[i];
       if (prim >= 0) {  // calculateDryFrictionVector, primitive part (Simulation.cpp:640-652)
         f3 n = ld3(rec_n, i, N);
-        f3 d = f - prim_vout(S.prims[prim], n) * m;
+        f3 d = prim_d(S.prims[prim], n, f, m, pvel_s);
         r = dry_friction(n, d, mu[S.prims[prim].group]);
       }
       st3(rec_f, i, N, f);
@@ -182,7 +184,7 @@ __device__ __forceinline__ void pd_step_pk(const DevSystem *__restrict__ Sp, con
         f3 r = mk(0, 0, 0);
         if (q.prim >= 0) {  // calculateDryFrictionVector, primitive part (Simulation.cpp:640-652)
           f3 n = ld3(rec_n, i, N);
-          f3 d = f - prim_vout(S.prims[q.prim], n) * q.m;
+          f3 d = prim_d(S.prims[q.prim], n, f, q.m, pvel_s);
           r = dry_friction(n, d, mu[S.prims[q.prim].group]);
         }
         st3(rec_f, i, N, f);

@@ -45,6 +45,7 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_res(const DevSystem *__rest
   int *rec_prim = A.rec_prim + (size_t) b * N;
   const float *xfix = A.x_fixed + (size_t) b * 3 * S.Af;
   const float *mu = A.mu + (size_t) b * S.ngroups;
+  const float *pvel_b = A.pvel ? A.pvel + (size_t) b * 3 * S.ngroups : nullptr;      // this step's obstacle velocities of this rollout (null: none set)
   const float h = S.h;
   const f3 grav = mk(S.gx, S.gy, S.gz);
   const f3 fu = A.fu ? mk(A.fu[3 * b], A.fu[3 * b + 1], A.fu[3 * b + 2]) : mk(0, 0, 0);
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_res(const DevSystem *__rest
     part += dot(v0, v0);
     int prim = -1;
     f3 nrm = mk(0, 0, 0);
-    if (S.contact_enabled) prim = detect_primitive(S, A.pcen + (size_t) b * 3 * S.nprim, ld3(xn, i, N), v0, nrm);
+    if (S.contact_enabled) prim = detect_primitive(S, A.pcen + (size_t) b * 3 * S.nprim, pvel_b, ld3(xn, i, N), v0, nrm);
     rec_prim[i] = prim;
     st3(rec_n, i, N, nrm);
     ncontact += (prim >= 0);
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_res(const DevSystem *__rest
         const int prim = rec_prim[i];
         if (prim >= 0) {  // calculateDryFrictionVector, primitive part (Simulation.cpp:640-652)
           f3 n = ld3(rec_n, i, N);
-          f3 d = f - prim_vout(S.prims[prim], n) * m;
+          f3 d = prim_d(S.prims[prim], n, f, m, pvel_b);
           r = dry_friction(n, d, mu[S.prims[prim].group]);
         }
         st3(rec_f, i, N, f);

@@ -171,12 +171,13 @@ def sim_step(sim, x, v, a):
 _ROLLOUT_INPUTS = ("x0", "v0", "actions", "uniform_force", "vertex_force_scale", "vertex_forces", "mu")
 
 
-def _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets=None):
+def _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets=None, primitive_velocities=None):
     """Checks the arguments of sim_rollout against the engine's sizes and returns the episode length T. Touches no device."""
     e = sim.engine
     B, N, Af, G = e.B, e.N, e.Af, e.ngroups
     given = dict(zip(_ROLLOUT_INPUTS, (x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu)))
     given["primitive_offsets"] = primitive_offsets
+    given["primitive_velocities"] = primitive_velocities
     if torch.is_tensor(primitive_offsets) and primitive_offsets.requires_grad:
         raise ValueError("sim_rollout: primitive_offsets requires grad, but there is no gradient with respect to an obstacle's centre: the adjoint "
                          "holds the contact normals of the record constant, as the reference's does. Pass primitive_offsets.detach()")
@@ -204,8 +205,9 @@ def _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scal
         if given[name] is not None and given[name].dim() > 0:
             T = int(given[name].shape[0])
             break
-    if T is None and primitive_offsets is not None and primitive_offsets.dim() == 4:
-        T = int(primitive_offsets.shape[0])
+    for name in ("primitive_offsets", "primitive_velocities"):
+        if T is None and given[name] is not None and given[name].dim() == 4:
+            T = int(given[name].shape[0])
     if T is None:
         if steps is None:
             raise ValueError("sim_rollout: no schedule given, pass steps=")
@@ -217,9 +219,9 @@ def _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scal
     want = dict(x0=(B, 3 * N), v0=(B, 3 * N), actions=(T, B, 3 * Af), uniform_force=(T, B, 3), vertex_force_scale=(T, B),
                 vertex_forces=(B, 3 * N), mu=(B, G))
     for name, t in given.items():
-        if name == "primitive_offsets":
+        if name in ("primitive_offsets", "primitive_velocities"):
             if t is not None and tuple(t.shape) not in ((T, B, G, 3), (B, G, 3)):
-                raise ValueError(f"sim_rollout: wrong shape: primitive_offsets is {tuple(t.shape)}, expected {(T, B, G, 3)} (one per step) or {(B, G, 3)}")
+                raise ValueError(f"sim_rollout: wrong shape: {name} is {tuple(t.shape)}, expected {(T, B, G, 3)} (one per step) or {(B, G, 3)}")
         elif t is not None and tuple(t.shape) != want[name]:
             raise ValueError(f"sim_rollout: wrong shape: {name} is {tuple(t.shape)}, expected {want[name]}")
     if T > e.tape:
@@ -233,11 +235,14 @@ def _np64(t):
 
 class RolloutFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, sim, T, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets=None):
+    def forward(ctx, sim, T, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets=None, primitive_velocities=None):
         e = sim.engine
         B, N = e.B, e.N
         if primitive_offsets is not None and primitive_offsets.dim() == 3:      # constant over the episode: the same entry in every step
             primitive_offsets = primitive_offsets.detach().unsqueeze(0).expand(T, *primitive_offsets.shape)
+        ctx.velocities_per_episode = primitive_velocities is not None and primitive_velocities.dim() == 3      # (its gradient: summed over the steps)
+        if ctx.velocities_per_episode:
+            primitive_velocities = primitive_velocities.detach().unsqueeze(0).expand(T, *primitive_velocities.shape)
         sim._episode += 1
         ctx.sim, ctx.T, ctx.episode = sim, T, sim._episode
         ctx.save_for_backward(vertex_forces, vertex_force_scale)
@@ -258,6 +263,8 @@ class RolloutFunction(torch.autograd.Function):
                 e.set_force_schedule_dev(0, T, fu=c(uniform_force), fv_scale=c(vertex_force_scale))
             if primitive_offsets is not None:
                 e.set_primitive_offset_schedule_dev(0, T, primitive_offsets.detach())
+            if primitive_velocities is not None:
+                e.set_primitive_velocity_schedule_dev(0, T, primitive_velocities.detach())
             e.rollout_forward_async(0, T)
             xs = torch.empty((T, B, 3 * N), dtype=x0.dtype, device=x0.device)
             vs = torch.empty_like(xs)
@@ -277,6 +284,8 @@ class RolloutFunction(torch.autograd.Function):
             e.set_force_schedule(0, T, fu=_np64(uniform_force), fv_scale=_np64(vertex_force_scale))
         if primitive_offsets is not None:
             e.set_primitive_offset_schedule(0, _np64(primitive_offsets))
+        if primitive_velocities is not None:
+            e.set_primitive_velocity_schedule(0, _np64(primitive_velocities))
         e.rollout_forward(0, T)
         xs, vs = e.get_states(1, T)
         sim.step_idx = T
@@ -291,6 +300,7 @@ class RolloutFunction(torch.autograd.Function):
             raise RuntimeError("sim_rollout: the tape holds a later episode; back-propagate an episode before the next sim_rollout on this BatchedSim")
         vertex_forces, vertex_force_scale = ctx.saved_tensors
         _, _, _, _, need_a, need_fu, need_fvs, need_fv, need_mu = ctx.needs_input_grad[:9]
+        need_w = len(ctx.needs_input_grad) > 10 and ctx.needs_input_grad[10]
         keep = bool(need_fvs or need_fv)
         sim._bwd_slots.update(range(1, T + 1))
         dt = grad_xs.dtype
@@ -317,8 +327,14 @@ class RolloutFunction(torch.autograd.Function):
             dfv = new(B, 3 * N) if need_fv else None
             if need_fu or keep:
                 e.get_force_schedule_gradients_dev(1, T, dfu=dfu, dfv_scale=dfvs, dfv=dfv)
+            dw = None
+            if need_w:
+                dw = new(T, B, G, 3)
+                e.get_primitive_velocity_gradients_dev(1, T, dw)
+                if ctx.velocities_per_episode:
+                    dw = dw.sum(0)
             sim.check_episode()                # the single synchronisation of the episode: errors of both sweeps surface here
-            return None, None, dx0, dv0, da, dfu, dfvs, dfv, dmu, None
+            return None, None, dx0, dv0, da, dfu, dfvs, dfv, dmu, None, dw
         gxs, gvs = _np64(grad_xs), _np64(grad_vs)
         e.keep_force_gradients(keep)
         zero = np.zeros((1, B, 3 * N))
@@ -337,12 +353,16 @@ class RolloutFunction(torch.autograd.Function):
             if need_fv:
                 w = np.ones((T, B)) if vertex_force_scale is None else _np64(vertex_force_scale)
                 dfv = t(np.einsum("kb,kbq->bq", w, y))
+        dw = None
+        if need_w:
+            dw = e.get_primitive_velocity_gradients(1, T)
+            dw = t(dw.sum(0) if ctx.velocities_per_episode else dw)
         sim.check_episode()
-        return None, None, t(dx0), t(dv0), da, dfu, dfvs, dfv, (t(dmu) if need_mu else None), None
+        return None, None, t(dx0), t(dv0), da, dfu, dfvs, dfv, (t(dmu) if need_mu else None), None, dw
 
 
 def sim_rollout(sim, x0, v0, actions=None, *, steps=None, uniform_force=None, vertex_force_scale=None, vertex_forces=None, mu=None,
-                primitive_offsets=None):
+                primitive_offsets=None, primitive_velocities=None):
     """A whole differentiable episode of all rollouts: the states after every step, (xs, vs), [T, B, 3N] each in the dtype of x0.
 
     x0, v0: [B, 3N] initial state. actions: [T, B, 3 Af] clip targets of every step. uniform_force: [T, B, 3] force on every vertex per
@@ -354,6 +374,14 @@ def sim_rollout(sim, x0, v0, actions=None, *, steps=None, uniform_force=None, ve
     (Engine.set_primitive_offset_schedule: the obstacle of group g is tested at fp32(center + offset)). When omitted the schedule is cleared
     like the others and the engine's current offsets (Engine.set_primitive_offsets; none by default) apply. A tensor that requires grad is
     refused: the adjoint holds the contact normals constant, as the reference's does, so no gradient with respect to the centre exists.
+
+    primitive_velocities: [T, B, G, 3] velocity of every primitive group per step and rollout, or [B, G, 3] for the whole episode
+    (Engine.set_primitive_velocity_schedule: the friction law sees the momentum relative to the moving obstacle, d = (f - v_rot m) - w m,
+    and the detection looks ahead along vel - w). When omitted the schedule is cleared like the others and the engine's current velocities
+    (Engine.set_primitive_velocities; none by default) apply. A tensor that requires grad receives dL/dw of every step, summed over the
+    steps for the [B, G, 3] form (normals and contact set held constant, as everywhere in the adjoint). The two go together: a caller who
+    moves an obstacle along c(t) passes offsets[s] = c(t_s) - c_built and velocities[s] = (c(t_{s+1}) - c(t_s)) / h — the offset is the
+    obstacle's position at the start of step s, and it moves by velocities[s] h during the step.
 
     The episode occupies tape slots 0 .. T (T <= the tape of alloc_batch) and replaces what the tape held: the function sets the trajectory
     start to slot 0, clears the schedules it does not set, and leaves sim.step_idx = T. `mu` and `vertex_forces`, when given, stay set on
@@ -367,5 +395,6 @@ def sim_rollout(sim, x0, v0, actions=None, *, steps=None, uniform_force=None, ve
 
     The action gradient is dL_dxfixed of every step as the adjoint gives it: it is NOT rescaled. The clamp of its norm belongs to
     `sim_step`, which mirrors the reference's per-step function (functional.py:88-97)."""
-    T = _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets)
-    return RolloutFunction.apply(sim, T, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets)
+    T = _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets, primitive_velocities)
+    return RolloutFunction.apply(sim, T, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets,
+                                 primitive_velocities)

@@ -334,9 +334,9 @@ int dc_clear_schedules(dc_ctx *ctx);
  *     centre_p = fp32( (double) dc_primitive.center_p + d[b][g] )          (the sum in fp64, rounded once)
  * so a context built at the moved centre and a context given the offset see the same fp32 centre, bit for bit. The children of a LowerLeg share
  * a group and move together (center_prim + child->centerInit in the reference). Nothing else of the primitive changes: radius, plane corners and
- * capsule axis (relative to the centre), mu, rotates, the discretised sphere's mesh (relative to the centre). The obstacle stays static in the
- * reference's sense (v_out has no translation term); an obstacle velocity is not modelled. The adjoint holds the contact normal of the record
- * constant, as the reference's does: there is no gradient w.r.t. the centre.
+ * capsule axis (relative to the centre), mu, rotates, the discretised sphere's mesh (relative to the centre). An offset alone leaves the obstacle
+ * static in the reference's sense (v_out has no translation term): a caller who MOVES an obstacle also gives its velocity, below. The adjoint holds
+ * the contact normal of the record constant, as the reference's does: there is no gradient w.r.t. the centre.
  * dc_set_primitive_offsets: offsets of the NEXT forward steps, like dc_set_uniform_force (d = B*G*3; NULL restores the built centres).
  * dc_set_primitive_offset_schedule: the step that advances slot slot0 + s to slot0 + s + 1 uses d[s] (nsteps*B*G*3); the rules of
  * dc_set_force_schedule hold — an entry stays until it is overwritten, dc_clear_schedules or dc_alloc_batch, the per-step calls honour it, and a
@@ -351,6 +351,43 @@ int dc_set_primitive_offset_schedule(dc_ctx *ctx, int slot0, int nsteps, const d
 int dc_set_primitive_offsets_dev(dc_ctx *ctx, const void *d_d /*B*G*3 or NULL*/, int is_f32);
 int dc_set_primitive_offset_schedule_dev(dc_ctx *ctx, int slot0, int nsteps, const void *d_d /*nsteps*B*G*3*/, int is_f32);
 int dc_get_primitive_centers(dc_ctx *ctx, int slot, double *c /*B*P*3*/);
+/* ---- moving obstacles: a velocity per rollout, primitive group and step. The reference carries the quantity (v_out = this->velocity in every
+ * isInContact of Primitive.cpp) and never sets it; without it a sphere moved through the cloth by a centre schedule brakes the cloth towards
+ * rest in the world frame. ONE rule, next to the centre rule above: rollout b, group g and step have w[b][g][3]; the device stores fp32(w), the
+ * fp64 operator of the adjoint uses (double) fp32(w). It enters the step in two places.
+ *  1. Friction, forward and adjoint: for a vertex in contact with a flattened primitive p of group g
+ *         d = (f - v_rot(p, n) m) - w[b][g] m            (v_rot: the rotating sphere's spin term; evaluated in this order, so w = +0 changes no bit)
+ *     in every forward kernel family, in the fp32 adjoint operators and in the fp64 operator and dL_dmu (recorded and dc_set_record branches).
+ *  2. Detection look-ahead: the sample points of group g become pos + (vel - w[b][g]) h k / 2, k = 0, 1, 2, tested against the step's centre:
+ *     the centre row is the obstacle's position at the START of the step and the obstacle moves by w h during it. (The reference's text uses the
+ *     absolute vel; the two agree wherever the reference is exercised, w = 0.) With both, the step is Galilean invariant: every obstacle moving at
+ *     w and the cloth at (x, v + w) — attachment targets moved by w h — is the static step at (x, v), shifted by (w h, w).
+ * A caller who moves an obstacle along c(t) passes offsets[s] = c(t_s) - c_built and velocities[s] = (c(t_{s+1}) - c(t_s)) / h.
+ * Storage: a table [slot][B][G][3], per GROUP, allocated by the first of these setters after dc_alloc_batch; until then the kernels evaluate the
+ * static law (a null pointer: one uniform branch in the forward kernels, and the adjoint step kernels of such a context are the instances compiled
+ * without the table). Row `slot` is what the step that PRODUCED `slot` used and what the backward step through record
+ * `slot` reads: a record handed in with dc_set_record at `slot` gets its velocity from a one-step schedule at slot - 1.
+ * dc_set_primitive_velocities: velocities of the NEXT forward steps without a schedule entry (w = B*G*3; NULL = zeros).
+ * dc_set_primitive_velocity_schedule: the step slot0 + s -> slot0 + s + 1 uses w[s]. The rules of the offset entries hold throughout: an entry
+ * stays until it is overwritten, dc_clear_schedules or dc_alloc_batch; the per-step calls honour it; a fused sweep needs it on all of its steps
+ * or on none (DC_ERR_INVALID); dc_alloc_batch, dc_set_primitives and dc_build drop everything; a host-only context answers DC_ERR_STATE;
+ * G == 0 gives DC_ERR_INVALID. The _dev forms take DEVICE pointers (fp32 or fp64) on the context's stream: one launch for all slots, no
+ * synchronisation.
+ * dc_get_primitive_velocities: the fp32 values, widened, that the step which produced `slot` used (zeros when none was ever set). Synchronises.
+ * The gradient: a velocity, unlike a centre, enters the adjoint smoothly (r depends on w only through d), so under the adjoint's own rules — normals
+ * constant, contact set not differentiated — every backward step leaves, in the convention of dL_dmu,
+ *         dL/dw[b][g] = -h * sum over the vertices i in contact with group g of  m_i (dr_i/dd_i)^T u_i
+ * summed in fp64 without atomics (bit-reproducible, one workgroup or split), written per record slot and OVERWRITTEN by the next backward step
+ * through that slot. dL_ddensity keeps the reference's omission of the dr/dd term (adddr_dd = false): a moving obstacle's step carries that
+ * omission exactly as the rotating sphere's does. The getters return slots slot0 .. slot0 + nslots - 1 (nslots*B*G*3) and fail with DC_ERR_STATE
+ * before any velocity setter; the host form synchronises, the _dev form is enqueued. There is still no gradient w.r.t. the centre.            */
+int dc_set_primitive_velocities(dc_ctx *ctx, const double *w /*B*G*3 or NULL = zeros*/);
+int dc_set_primitive_velocity_schedule(dc_ctx *ctx, int slot0, int nsteps, const double *w /*nsteps*B*G*3*/);
+int dc_set_primitive_velocities_dev(dc_ctx *ctx, const void *d_w /*B*G*3 or NULL = zeros*/, int is_f32);
+int dc_set_primitive_velocity_schedule_dev(dc_ctx *ctx, int slot0, int nsteps, const void *d_w /*nsteps*B*G*3*/, int is_f32);
+int dc_get_primitive_velocities(dc_ctx *ctx, int slot, double *w /*B*G*3*/);
+int dc_get_primitive_velocity_gradients(dc_ctx *ctx, int slot0, int nslots, double *dL_dw /*nslots*B*G*3*/);
+int dc_get_primitive_velocity_gradients_dev(dc_ctx *ctx, int slot0, int nslots, void *d_dL_dw /*nslots*B*G*3*/, int is_f32);
 /* states of nslots consecutive slots in one call: x[k*B*3N ...], v likewise (either may be NULL) */
 int dc_get_states(dc_ctx *ctx, int slot0, int nslots, double *x, double *v);
 /* dL_dxfixed of the steps through records slot0 .. slot0+nslots-1 of the last backward sweep / step (B*3Af each) */
