@@ -69,6 +69,8 @@ EXPORTED_SYMBOLS = [
     "dc_get_primitive_centers",
     "dc_set_primitive_velocities", "dc_set_primitive_velocity_schedule", "dc_set_primitive_velocities_dev", "dc_set_primitive_velocity_schedule_dev",
     "dc_get_primitive_velocities", "dc_get_primitive_velocity_gradients", "dc_get_primitive_velocity_gradients_dev",
+    "dc_set_primitive_shapes", "dc_set_primitive_shape_schedule", "dc_set_primitive_shapes_dev", "dc_set_primitive_shape_schedule_dev",
+    "dc_get_primitive_shapes",
 ]
 
 _lib = None
@@ -127,6 +129,7 @@ class Engine:
         self.B = 0
         self.ngroups = 1
         self.nprims = 0
+        self._built_shapes = np.zeros((0, 8))
 
     def close(self):
         if getattr(self, "h", None):
@@ -196,6 +199,8 @@ class Engine:
                 groups.append(arr[k].group)
         self.ngroups = max(len(groups), 1)
         self.nprims = len(prims)
+        self._built_shapes = np.array([[arr[k].top_offset[d] for d in range(3)] + [arr[k].corner2[d] for d in range(3)] + [arr[k].radius, arr[k].length]
+                                       for k in range(len(prims))], dtype=np.float64).reshape(len(prims), 8)
         self._chk(self.lib.dc_set_primitives(self.h, C.c_int(len(prims)), arr))
 
     def build(self):
@@ -291,6 +296,28 @@ class Engine:
         """[nslots][B][G][3] dL/dw of the backward steps through records slot0 .. slot0+nslots-1 (dc_get_primitive_velocity_gradients)"""
         out = np.zeros((nslots, self.B, self.ngroups, 3))
         self._chk(self.lib.dc_get_primitive_velocity_gradients(self.h, C.c_int(slot0), C.c_int(nslots), _d(out)))
+        return out
+
+    def built_primitive_shapes(self):
+        """[P][8] float64 shape rows {top_offset[3], corner2[3], radius, length} of the dicts last given to set_primitives, unrounded: what
+        set_primitive_shapes takes per rollout (host side, no C call)"""
+        return self._built_shapes.copy()
+
+    def set_primitive_shapes(self, s):
+        """s: [B][P][8] shape rows {top_offset[3], corner2[3], radius, length} of the flattened primitives for the NEXT forward steps
+        (dc_set_primitive_shapes: stored as fp32, read by the kernels in place of the built values); None restores the built shapes"""
+        a = None if s is None else self._vec(s, 8 * self.nprims)
+        self._chk(self.lib.dc_set_primitive_shapes(self.h, _d(a)))
+
+    def set_primitive_shape_schedule(self, slot0, s):
+        """s: [nsteps][B][P][8]: the step slot0+k -> slot0+k+1 uses s[k] (dc_set_primitive_shape_schedule)"""
+        s = np.ascontiguousarray(np.asarray(s, dtype=np.float64).reshape(-1, self.B, self.nprims, 8))
+        self._chk(self.lib.dc_set_primitive_shape_schedule(self.h, C.c_int(slot0), C.c_int(s.shape[0]), _d(s)))
+
+    def get_primitive_shapes(self, slot):
+        """[B][P][8] shape rows that the step which produced `slot` used (fp32 values, widened; the built shapes when none was ever set)"""
+        out = np.zeros((self.B, self.nprims, 8))
+        self._chk(self.lib.dc_get_primitive_shapes(self.h, C.c_int(slot), _d(out)))
         return out
 
     def get_force_gradient(self):
@@ -527,6 +554,18 @@ class Engine:
         self._velocity_schedule_dev = w = w.contiguous()
         (p,), f = self._tps((w, self.B * self.ngroups * 3, nsteps))
         self._chk(self.lib.dc_set_primitive_velocity_schedule_dev(self.h, C.c_int(slot0), C.c_int(nsteps), p, C.c_int(f)))
+
+    def set_primitive_shapes_dev(self, s):
+        """dc_set_primitive_shapes from a CUDA tensor [B][P][8] (a non-contiguous view is copied first); None restores the built shapes"""
+        self._shapes_dev = s = None if s is None else s.contiguous()      # (kept alive until the next call: the conversion is only enqueued)
+        (p,), f = self._tps((s, self.B * self.nprims * 8, 1))
+        self._chk(self.lib.dc_set_primitive_shapes_dev(self.h, p, C.c_int(f)))
+
+    def set_primitive_shape_schedule_dev(self, slot0, nsteps, s):
+        """dc_set_primitive_shape_schedule from a CUDA tensor [nsteps][B][P][8] (a non-contiguous view is copied first)"""
+        self._shape_schedule_dev = s = s.contiguous()
+        (p,), f = self._tps((s, self.B * self.nprims * 8, nsteps))
+        self._chk(self.lib.dc_set_primitive_shape_schedule_dev(self.h, C.c_int(slot0), C.c_int(nsteps), p, C.c_int(f)))
 
     def get_primitive_velocity_gradients_dev(self, slot0, nslots, dw):
         """dL/dw of the backward steps through records slot0 .. slot0+nslots-1 into a contiguous CUDA tensor [nslots][B][G][3]"""

@@ -89,6 +89,17 @@ struct dc_ctx {
   float *pv_cur = nullptr;          // [B][G][3] velocities of the NEXT steps that have no schedule entry
   float *DPV = nullptr;             // [(tape+1)][B][G][3] dL/dw of the backward step through record `slot` (overwritten per step)
   std::vector<char> sched_pv;
+  // obstacle shapes (dc_set_primitive_shapes / dc_set_primitive_shape_schedule, dc_primshape.h): fp32 rows {top_offset, corner2, radius, length}
+  // per flattened primitive. Allocated by the first shape setter after dc_alloc_batch and filled with the built shapes; while PS is null the
+  // kernels get a null pointer and read DevPrim. Row `slot` of PS is what the step that produced `slot` used.
+  float *PS = nullptr;              // [(tape+1)][B][P][8]
+  float *ps_cur = nullptr;          // [B][P][8] shapes of the NEXT steps that have no schedule entry
+  const float *ps_built = nullptr;  // [B][P][8] the built shapes (what dc_set_primitive_shapes_dev(NULL) restores without a synchronisation)
+  // which version of ps_cur a row of PS holds, the scheme of pc_row_gen: 0 = the built shapes, -1 = a schedule entry, > 0 = the ps_cur of that
+  // dc_set_primitive_shapes call
+  std::vector<int> ps_row_gen;
+  int ps_gen = 0, ps_gen_last = 0;
+  std::vector<char> sched_ps;
   void *comm = nullptr;             // RCCL communicator of dc_comm_init (ncclComm_t), one rank per context
   int comm_ranks = 0;
   std::vector<void *> sched_pool;

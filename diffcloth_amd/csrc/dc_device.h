@@ -197,6 +197,11 @@ struct FwdArgs {
   // table stepped by slot_pvel = B * ngroups * 3; NULL until a velocity is set for the first time: the kernels then evaluate the static law
   const float *pvel;
   size_t slot_pvel;
+  // fp32 shape rows {top_offset[3], corner2[3], radius, length} of the flattened primitives in this step, [B][nprim][8] (dc_set_primitive_shapes /
+  // ..._schedule), a row of the per-slot table stepped by slot_pshp = B * nprim * 8; NULL until a shape is set for the first time: the kernels
+  // then read the shape fields of DevPrim
+  const float *pshp;
+  size_t slot_pshp;
 };
 
 // (BwdArgsStatic: what the adjoint step kernels of a context WITHOUT an obstacle-velocity table take by value — their argument block, and with it

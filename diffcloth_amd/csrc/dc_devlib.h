@@ -119,20 +119,26 @@ __device__ __forceinline__ f3 dri_dmu(f3 n, f3 d, float mu) {
 }
 
 // Primitive::isInContact family (Sphere Primitive.cpp:221-261, Capsule :570-604, Plane :66-130, Bowl :362-381) for one
-// flattened primitive, tested at centre c: the step's centre of this rollout (FwdArgs::pcen), not DevPrim::cx/cy/cz.
-__device__ __forceinline__ bool prim_in_contact(const DevPrim &p, f3 c, f3 pos, f3 &normal) {
+// flattened primitive, tested at centre c: the step's centre of this rollout (FwdArgs::pcen), not DevPrim::cx/cy/cz, and with the eight
+// shape values sh the caller loaded: the step's row of this rollout (FwdArgs::pshp) or, while no shape was ever set, DevPrim's fields.
+struct PrimShape {
+  float tx, ty, tz;      // capsule: top offset; plane: corner upperLeft relative to the centre
+  float ux, uy, uz;      // plane: corner upperRight relative to the centre
+  float radius, length;
+};
+__device__ __forceinline__ bool prim_in_contact(int kind, const PrimShape &p, f3 c, f3 pos, f3 &normal) {
   f3 q = pos - c;
-  if (p.kind == DC_PRIM_SPHERE || p.kind == DC_PRIM_SPHERE_DISCRETIZED) {      // (discretised: the normal is replaced by detect_primitive)
+  if (kind == DC_PRIM_SPHERE || kind == DC_PRIM_SPHERE_DISCRETIZED) {      // (discretised: the normal is replaced by detect_primitive)
     float dist = sqrtf(dot(q, q)) - p.radius;
     normal = normalized(q);
     return dist < 0.1f;
   }
-  if (p.kind == DC_PRIM_BOWL) {     // Bowl::isInContact (Primitive.cpp:362-381): inside of the lower half of a shell, eps 0.005
+  if (kind == DC_PRIM_BOWL) {     // Bowl::isInContact (Primitive.cpp:362-381): inside of the lower half of a shell, eps 0.005
     const float len = sqrtf(dot(q, q));
     normal = q * (-1.0f / len);
     return (len - p.radius <= 0.005f) && !(pos.y > c.y) && (len > p.radius - 0.005f);
   }
-  if (p.kind == DC_PRIM_PLANE) {    // Plane::isInContact (Primitive.cpp:66-130): finite rectangle, eps 0.4, thickness 5, edge tol 5e-4
+  if (kind == DC_PRIM_PLANE) {    // Plane::isInContact (Primitive.cpp:66-130): finite rectangle, eps 0.4, thickness 5, edge tol 5e-4
     const f3 ul = mk(p.tx, p.ty, p.tz), ur = mk(p.ux, p.uy, p.uz), lr = ul * -1.0f, ll = ur * -1.0f;
     const float eps = 0.4f, edge_tol = 0.0005f;
     const float br = sqrtf(fmaxf(dot(ul, ul), dot(ur, ur)));
@@ -217,9 +223,13 @@ __device__ __attribute__((noinline)) void sphere_mesh_normal(const DevSystem &S,
 // when no velocity was ever set. cen is the obstacle's position at the START of the step and the obstacle moves by w h during it: the
 // samples of group g are pos + (vel - w[g]) h k / 2, the look-ahead in the obstacle's frame (w = +0 gives vel - 0 = vel bit for bit).
 // Like cen, every caller of one step passes the same row.
-__device__ __attribute__((noinline)) int detect_primitive(const DevSystem &S, const float *cen, const float *wv, f3 pos, f3 vel, f3 &normal) {
+// shp: the shape rows [nprim][8] = {top_offset[3], corner2[3], radius, length} of THIS rollout in THIS step (a row of the table FwdArgs::pshp
+// points into), or null when no shape was ever set: then the same eight fields of DevPrim, one uniform branch. A discretised sphere always
+// takes DevPrim's (its face table is built for one radius). Like cen, every caller of one step passes the same row.
+__device__ __attribute__((noinline)) int detect_primitive(const DevSystem &S, const float *cen, const float *wv, const float *shp, f3 pos, f3 vel, f3 &normal) {
   const float DC_G *cg = (const float DC_G *) cen;
   const float DC_G *wg = (const float DC_G *) wv;
+  const float DC_G *sg = (const float DC_G *) shp;
   int p0 = 0;
   while (p0 < S.nprim) {
     int p1 = p0;
@@ -231,7 +241,16 @@ __device__ __attribute__((noinline)) int detect_primitive(const DevSystem &S, co
       f3 q = pos + vr * (S.h * 0.5f * (float) k);
       for (int p = p0; p < p1; p++) {
         const f3 c = mk(cg[3 * p], cg[3 * p + 1], cg[3 * p + 2]);
-        if (prim_in_contact(S.prims[p], c, q, normal)) {
+        const int kind = S.prims[p].kind;
+        PrimShape sh;
+        if (shp && kind != DC_PRIM_SPHERE_DISCRETIZED) {
+          const float DC_G *r = sg + 8 * p;
+          sh.tx = r[0]; sh.ty = r[1]; sh.tz = r[2]; sh.ux = r[3]; sh.uy = r[4]; sh.uz = r[5]; sh.radius = r[6]; sh.length = r[7];
+        } else {
+          const DevPrim &d = S.prims[p];
+          sh.tx = d.tx; sh.ty = d.ty; sh.tz = d.tz; sh.ux = d.ux; sh.uy = d.uy; sh.uz = d.uz; sh.radius = d.radius; sh.length = d.length;
+        }
+        if (prim_in_contact(kind, sh, c, q, normal)) {
           if (S.prims[p].kind == DC_PRIM_SPHERE_DISCRETIZED && S.dsph_ntri > 0) {
             const double ts = S.h64 * (0.5 * (double) k);
             // (the sample point re-formed in fp64 from its fp32 terms, the relative velocity vel - w among them)

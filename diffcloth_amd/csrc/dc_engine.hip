@@ -11,6 +11,7 @@
 #include "dc_context.h"
 #include "dc_env.h"
 #include "dc_primoffset.h"
+#include "dc_primshape.h"
 #include "dc_record.h"
 #include "dc_tables.h"
 #include "dc_spheremesh.h"
@@ -72,6 +73,18 @@ float *pc_slot(const dc_ctx *c, int slot) { return c->PC + pc_elems(c) * slot; }
 size_t pv_elems(const dc_ctx *c) { return (size_t) c->B * c->ngroups * 3; }
 float *pv_slot(const dc_ctx *c, int slot) { return c->PV + pv_elems(c) * slot; }
 float *dpv_slot(const dc_ctx *c, int slot) { return c->DPV + pv_elems(c) * slot; }
+size_t ps_elems(const dc_ctx *c) { return (size_t) c->B * c->S.nprim * kShapeRow; }
+float *ps_slot(const dc_ctx *c, int slot) { return c->PS + ps_elems(c) * slot; }
+// one rollout's built rows, [P][8], as dc_build rounded them
+void built_shape_rows(const dc_ctx *c, std::vector<float> &rows) {
+  const int P = c->S.nprim;
+  rows.assign((size_t) P * kShapeRow, 0.0f);
+  for (int p = 0; p < P; p++) {
+    double row[kShapeRow];
+    primitive_shape_row(c->prims[p], row);
+    round_shape_row(row, rows.data() + (size_t) p * kShapeRow);
+  }
+}
 float *seedx_slot(const dc_ctx *c, int slot) { return c->SEEDX + slot_elems(c) * slot; }
 float *seedv_slot(const dc_ctx *c, int slot) { return c->SEEDV + slot_elems(c) * slot; }
 SelfRec self_slot(const dc_ctx *c, int slot) {      // self contacts of record `slot`
@@ -149,6 +162,7 @@ FwdArgs fwd_args(dc_ctx *c, int slot) {
   A.fv_scale = nullptr; A.slot_xfix = 0; A.slot_fu = 0; A.slot_fvs = 0;
   A.pcen = pc_slot(c, slot + 1); A.slot_pcen = pc_elems(c);      // (enqueue_forward_steps has brought the rows up to date)
   A.pvel = c->PV ? pv_slot(c, slot + 1) : nullptr; A.slot_pvel = c->PV ? pv_elems(c) : 0;      // (likewise; null = no velocity was ever set)
+  A.pshp = c->PS ? ps_slot(c, slot + 1) : nullptr; A.slot_pshp = c->PS ? ps_elems(c) : 0;      // (likewise; null = no shape was ever set: DevPrim's)
   // scheduled values of this step (dc_set_*_schedule) take precedence over the current ones
   if (c->S.Af > 0 && c->sched_xf[slot + 1]) A.x_fixed = xf_slot(c, slot + 1);
   if (c->sched_fu[slot + 1]) A.fu = c->FU_S + (size_t) c->B * 3 * (slot + 1);
@@ -518,10 +532,13 @@ int enqueue_forward_steps(dc_ctx *c, int slot, int nsteps, bool carry_targets, i
   int rc;
   FwdArgs FA = fwd_args(c, slot);          // fused: points x_fixed / fu / fv_scale at the first step's schedule entries
   if (fused) {      // a schedule (dc_set_*_schedule) has to cover all steps of a fused sweep or none of them
-    int nxf = 0, nfu = 0, nfvs = 0, npc = 0, npv = 0;
-    for (int k = 1; k <= nsteps; k++) { nxf += c->sched_xf[slot + k]; nfu += c->sched_fu[slot + k]; nfvs += c->sched_fvs[slot + k]; npc += c->sched_pc[slot + k]; npv += c->sched_pv[slot + k]; }
-    if ((nxf % nsteps) || (nfu % nsteps) || (nfvs % nsteps) || (npc % nsteps) || (npv % nsteps))
-      return fail(c, DC_ERR_INVALID, "dc_rollout_forward: a fixed-point / force / primitive-offset / primitive-velocity schedule covers only part of the steps " + std::to_string(slot) + " .. " + std::to_string(slot + nsteps));
+    int nxf = 0, nfu = 0, nfvs = 0, npc = 0, npv = 0, nps = 0;
+    for (int k = 1; k <= nsteps; k++) {
+      nxf += c->sched_xf[slot + k]; nfu += c->sched_fu[slot + k]; nfvs += c->sched_fvs[slot + k]; npc += c->sched_pc[slot + k]; npv += c->sched_pv[slot + k];
+      nps += c->sched_ps[slot + k];
+    }
+    if ((nxf % nsteps) || (nfu % nsteps) || (nfvs % nsteps) || (npc % nsteps) || (npv % nsteps) || (nps % nsteps))
+      return fail(c, DC_ERR_INVALID, "dc_rollout_forward: a fixed-point / force / primitive-offset / primitive-velocity / primitive-shape schedule covers only part of the steps " + std::to_string(slot) + " .. " + std::to_string(slot + nsteps));
     if (nxf) FA.slot_xfix = xf_elems(c);
     if (nfu) FA.slot_fu = (size_t) c->B * 3;
     if (nfvs && FA.fv_scale) FA.slot_fvs = (size_t) c->B;
@@ -536,6 +553,11 @@ int enqueue_forward_steps(dc_ctx *c, int slot, int nsteps, bool carry_targets, i
     }
     // likewise the obstacle velocities, once a context has them: the row of an unscheduled step takes the current set
     if (c->PV && !c->sched_pv[slot + k + 1]) HIPCHK(c, hipMemcpyAsync(pv_slot(c, slot + k + 1), c->pv_cur, sizeof(float) * pv_elems(c), hipMemcpyDeviceToDevice, c->stream));
+    // and the obstacle shapes: like the centres, a row is copied only when the current set changed since it was written
+    if (c->PS && !c->sched_ps[slot + k + 1] && c->ps_row_gen[slot + k + 1] != c->ps_gen) {
+      HIPCHK(c, hipMemcpyAsync(ps_slot(c, slot + k + 1), c->ps_cur, sizeof(float) * ps_elems(c), hipMemcpyDeviceToDevice, c->stream));
+      c->ps_row_gen[slot + k + 1] = c->ps_gen;
+    }
     if (fused) continue;
     if (k) FA = fwd_args(c, slot + k);
     if (self_on) launch_self_detect(c->S, c->W, FA, c->B, c->stream);
@@ -873,9 +895,8 @@ int dc_build(dc_ctx *c) {
     }
     DevPrim &d = S.prims[k];
     d.kind = q.kind; d.group = c->group_of_prim[k]; d.rotates = q.rotates; d.pad = 0;
-    d.cx = (float) q.center[0]; d.cy = (float) q.center[1]; d.cz = (float) q.center[2]; d.radius = (float) q.radius;
-    d.tx = (float) q.top_offset[0]; d.ty = (float) q.top_offset[1]; d.tz = (float) q.top_offset[2]; d.length = (float) q.length;
-    d.ux = (float) q.corner2[0]; d.uy = (float) q.corner2[1]; d.uz = (float) q.corner2[2]; d.pad2 = 0.f;
+    d.cx = (float) q.center[0]; d.cy = (float) q.center[1]; d.cz = (float) q.center[2]; d.pad2 = 0.f;
+    primitive_shape_to_prim(q, d);      // radius, top_offset, length, corner2: the rule of dc_primshape.h, shared with dc_set_primitive_shapes
   }
   {  // device-resident copy of the descriptor itself (kernels take a pointer to it)
     DevSystem *dS = nullptr;
@@ -1049,6 +1070,19 @@ int dc_alloc_batch(dc_ctx *c, int B, int tape) {
     c->pc_gen = 0; c->pc_gen_last = 0;
   }
   c->PV = c->pv_cur = c->DPV = nullptr; c->sched_pv.assign(slots + 1, 0);      // obstacle velocities: allocated by their first setter
+  c->PS = c->ps_cur = nullptr; c->sched_ps.assign(slots + 1, 0);      // obstacle shapes: likewise
+  c->ps_row_gen.assign(slots + 1, 0); c->ps_gen = 0; c->ps_gen_last = 0;
+  {   // ... but the built rows of the batch go up now, while this call synchronises anyway: the first shape setter, which may be a _dev form
+      // between enqueued sweeps, then fills table and current set with device-to-device copies on the stream
+    std::vector<float> one;
+    built_shape_rows(c, one);
+    std::vector<float> all((size_t) B * one.size());
+    for (int b = 0; b < B; b++) std::copy(one.begin(), one.end(), all.begin() + (size_t) b * one.size());
+    float *pb = nullptr;
+    if ((rc = dev_alloc(c, pool, &pb, all.size()))) return rc;
+    if (!all.empty()) HIPCHK(c, hipMemcpy(pb, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
+    c->ps_built = pb;
+  }
   c->SEEDX = c->SEEDV = nullptr;
   c->INJ_X = c->INJ_F = c->INJ_N = c->INJ_SN = c->INJ_SD = nullptr; c->inj_slot = -1;
   c->YS = nullptr; c->keep_y = false;
@@ -1537,6 +1571,7 @@ int dc_clear_schedules(dc_ctx *c) {
   std::fill(c->sched_fvs.begin(), c->sched_fvs.end(), 0); std::fill(c->sched_seed.begin(), c->sched_seed.end(), 0);
   std::fill(c->sched_pc.begin(), c->sched_pc.end(), 0);      // (the rows keep their entries until a step overwrites them: pc_row_gen = -1)
   std::fill(c->sched_pv.begin(), c->sched_pv.end(), 0);
+  std::fill(c->sched_ps.begin(), c->sched_ps.end(), 0);      // (like the centres: the rows keep their entries until a step overwrites them, ps_row_gen = -1)
   return DC_OK;
 }
 
@@ -1724,6 +1759,113 @@ int dc_get_primitive_velocity_gradients_dev(dc_ctx *c, int slot0, int nslots, vo
   HIPCHK(c, hipSetDevice(c->device));
   launch_copy_cast(dpv_slot(c, slot0), d_dL_dw, is_f32, (long) (pv_elems(c) * nslots), c->stream);
   HIPCHK(c, hipGetLastError());
+  return DC_OK;
+}
+
+// ---- obstacle shapes: a row {top_offset[3], corner2[3], radius, length} per rollout, flattened primitive and step (dc_primshape.h holds the
+//      conversion, shared with dc_build's DevPrim fill: a context given a shape equals a context built with it) ----
+namespace {
+// The shape table and its current set come with the first setter after dc_alloc_batch, every row holding the built shapes: a context that
+// never calls one hands a null pointer to its kernels, which then read DevPrim.
+int ensure_shapes(dc_ctx *c) {
+  if (c->PS) return DC_OK;
+  const size_t per = ps_elems(c), slots = (size_t) c->tape + 1;
+  float *ps = nullptr, *cur = nullptr;
+  int rc;
+  if ((rc = dev_alloc(c, c->batch_allocs, &ps, per * slots))) return rc;
+  if ((rc = dev_alloc(c, c->batch_allocs, &cur, per))) return rc;
+  // (enqueued, no synchronisation: ps_built has been on the device since dc_alloc_batch)
+  HIPCHK(c, hipMemcpyAsync(cur, c->ps_built, per * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  for (size_t s = 0; s < slots; s++) { HIPCHK(c, hipMemcpyAsync(ps + per * s, c->ps_built, per * sizeof(float), hipMemcpyDeviceToDevice, c->stream)); }
+  c->PS = ps; c->ps_cur = cur;      // (steps enqueued from here on see the table; those already enqueued read DevPrim: the same values)
+  c->ps_row_gen.assign(slots + 1, 0); c->ps_gen = 0; c->ps_gen_last = 0;
+  return DC_OK;
+}
+// rows x [P][8] host values -> fp32 in `dst`; null = the built shapes. Refuses non-finite values and, for a discretised sphere (whose face table
+// was built for one radius and whose row the kernels do not read), a row that differs from the built one after rounding. Synchronises.
+int upload_shapes(dc_ctx *c, const char *who, const double *s, float *dst, long rows) {
+  const int P = c->S.nprim;
+  std::vector<float> one;
+  built_shape_rows(c, one);
+  std::vector<float> v((size_t) rows * P * kShapeRow);
+  for (long r = 0; r < rows; r++)
+    for (int p = 0; p < P; p++) {
+      float *out = v.data() + ((size_t) r * P + p) * kShapeRow;
+      const float *built = one.data() + (size_t) p * kShapeRow;
+      if (!s) { std::copy(built, built + kShapeRow, out); continue; }
+      const double *in = s + ((size_t) r * P + p) * kShapeRow;
+      for (int k = 0; k < kShapeRow; k++)
+        if (!std::isfinite(in[k])) return fail(c, DC_ERR_INVALID, std::string(who) + ": non-finite shape value");
+      round_shape_row(in, out);
+      if (c->prims[p].kind == DC_PRIM_SPHERE_DISCRETIZED && std::memcmp(out, built, sizeof(float) * kShapeRow) != 0)
+        return fail(c, DC_ERR_INVALID, std::string(who) + ": the shape of a discretised sphere cannot change (its face table is built for one radius)");
+    }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (!v.empty()) HIPCHK(c, hipMemcpy(dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
+  return DC_OK;
+}
+}  // namespace
+
+int dc_set_primitive_shapes(dc_ctx *c, const double *s) {
+  int rc = check_offsets(c, "dc_set_primitive_shapes", 0, 0);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = ensure_shapes(c))) return rc;
+  if ((rc = upload_shapes(c, "dc_set_primitive_shapes", s, c->ps_cur, c->B))) return rc;
+  c->ps_gen = s ? ++c->ps_gen_last : 0;
+  return DC_OK;
+}
+
+int dc_set_primitive_shapes_dev(dc_ctx *c, const void *d_s, int is_f32) {
+  int rc = check_offsets(c, "dc_set_primitive_shapes_dev", 0, 0);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = ensure_shapes(c))) return rc;
+  if (d_s) launch_cast_in(d_s, is_f32, c->ps_cur, (long) ps_elems(c), c->stream);
+  else HIPCHK(c, hipMemcpyAsync(c->ps_cur, c->ps_built, sizeof(float) * ps_elems(c), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipGetLastError());
+  c->ps_gen = d_s ? ++c->ps_gen_last : 0;
+  return DC_OK;
+}
+
+int dc_set_primitive_shape_schedule(dc_ctx *c, int slot0, int nsteps, const double *s) {
+  int rc = check_offsets(c, "dc_set_primitive_shape_schedule", slot0, slot0 + nsteps);
+  if (rc) return rc;
+  if (nsteps < 1 || !s) return fail(c, DC_ERR_INVALID, "dc_set_primitive_shape_schedule: null schedule");
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = ensure_shapes(c))) return rc;
+  if ((rc = upload_shapes(c, "dc_set_primitive_shape_schedule", s, ps_slot(c, slot0 + 1), (long) nsteps * c->B))) return rc;
+  for (int k = 1; k <= nsteps; k++) { c->sched_ps[slot0 + k] = 1; c->ps_row_gen[slot0 + k] = -1; }
+  return DC_OK;
+}
+
+int dc_set_primitive_shape_schedule_dev(dc_ctx *c, int slot0, int nsteps, const void *d_s, int is_f32) {
+  int rc = check_offsets(c, "dc_set_primitive_shape_schedule_dev", slot0, slot0 + nsteps);
+  if (rc) return rc;
+  if (nsteps < 1 || !d_s) return fail(c, DC_ERR_INVALID, "dc_set_primitive_shape_schedule_dev: null schedule");
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = ensure_shapes(c))) return rc;
+  launch_cast_in(d_s, is_f32, ps_slot(c, slot0 + 1), (long) (ps_elems(c) * nsteps), c->stream);      // one launch for all slots
+  HIPCHK(c, hipGetLastError());
+  for (int k = 1; k <= nsteps; k++) { c->sched_ps[slot0 + k] = 1; c->ps_row_gen[slot0 + k] = -1; }
+  return DC_OK;
+}
+
+int dc_get_primitive_shapes(dc_ctx *c, int slot, double *s) {
+  int rc = check_batch(c, slot, slot);
+  if (rc) return rc;
+  if (slot < 1 || !s) return fail(c, DC_ERR_INVALID, "dc_get_primitive_shapes: slot 0 has no record");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<float> v(ps_elems(c));
+  if (c->PS) {
+    if (!v.empty()) HIPCHK(c, hipMemcpy(v.data(), ps_slot(c, slot), v.size() * sizeof(float), hipMemcpyDeviceToHost));
+  } else {      // no shape was ever set: the step read DevPrim
+    std::vector<float> one;
+    built_shape_rows(c, one);
+    for (int b = 0; b < c->B; b++) std::copy(one.begin(), one.end(), v.begin() + (size_t) b * one.size());
+  }
+  for (size_t k = 0; k < v.size(); k++) s[k] = v[k];
   return DC_OK;
 }
 

@@ -157,6 +157,8 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_cl(const DevSystem *__restr
   const float *pcen_s = A.pcen + (size_t) step * A.slot_pcen;      // this step's primitive centres, all rollouts
   const float *pvel_s = A.pvel ? A.pvel + (size_t) step * A.slot_pvel + (size_t) b * 3 * S.ngroups : nullptr;      // this step's obstacle velocities of this rollout (null: none set)
   const float *pvel_all = A.pvel ? A.pvel + (size_t) step * A.slot_pvel : nullptr;
+  const float *pshp_all = A.pshp ? A.pshp + (size_t) step * A.slot_pshp : nullptr;      // this step's obstacle shapes, all rollouts (null: DevPrim's)
+  const float *pshp_s = pshp_all ? pshp_all + (size_t) b * 8 * S.nprim : nullptr;
   // the tape state and f / r are read across parts: write-through stores, L1-bypassing loads (xnb, vinb, rfb, rrb, xob, vob)
   const BufVec xnb = buf_vec(A.x_in + off + so, N, X.same_xcd), vinb = buf_vec(A.v_in + off + so, N, X.same_xcd);
   const BufVec rfb = buf_vec(A.rec_f + off + so, N, X.same_xcd), rrb = buf_vec(A.rec_r + off + so, N, X.same_xcd);
@@ -168,7 +170,7 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_cl(const DevSystem *__restr
   if constexpr (DETECT) {                     // detection + layering of this step: part 0, then the lists change hands
     X.site = 2;
     if (part == 0) {
-      self_detect_rollout<THREADS>(S, W, b, A.x_in + so, A.v_in + so, A.rec_prim + (size_t) step * A.slot_prim, srec, fu_s, A.fv, fvs_s, pcen_s, pvel_all, (int *) lds, A.fv2);
+      self_detect_rollout<THREADS>(S, W, b, A.x_in + so, A.v_in + so, A.rec_prim + (size_t) step * A.slot_prim, srec, fu_s, A.fv, fvs_s, pcen_s, pvel_all, pshp_all, (int *) lds, A.fv2);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the lists have left the CU before the exchange below tells the other parts they exist
       __syncthreads();
     }
@@ -204,7 +206,7 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_cl(const DevSystem *__restr
     part_s += dot(v0, v0);
     int prim = -1;
     f3 nrm = mk(0, 0, 0);
-    if (S.contact_enabled) prim = detect_primitive(S, pcen_s + (size_t) b * 3 * S.nprim, pvel_s, ld3c(xnb, i), v0, nrm);
+    if (S.contact_enabled) prim = detect_primitive(S, pcen_s + (size_t) b * 3 * S.nprim, pvel_s, pshp_s, ld3c(xnb, i), v0, nrm);
     rec_prim[i] = prim;
     st3(rec_n, i, N, nrm);
     ncontact += (prim >= 0);

@@ -83,11 +83,13 @@ __device__ __forceinline__ void pd_step_pk(const DevSystem *__restrict__ Sp, con
   const float *pcen_s = A.pcen + (size_t) step * A.slot_pcen;      // this step's primitive centres, all rollouts
   const float *pvel_s = A.pvel ? A.pvel + (size_t) step * A.slot_pvel + (size_t) b * 3 * S.ngroups : nullptr;      // this step's obstacle velocities of this rollout (null: none set)
   const float *pvel_all = A.pvel ? A.pvel + (size_t) step * A.slot_pvel : nullptr;
+  const float *pshp_all = A.pshp ? A.pshp + (size_t) step * A.slot_pshp : nullptr;      // this step's obstacle shapes, all rollouts (null: DevPrim's)
+  const float *pshp_s = pshp_all ? pshp_all + (size_t) b * 8 * S.nprim : nullptr;
   SelfRec srec = A.self;                      // self contacts of this step's record
   srec.pair += (size_t) step * A.slot_self; srec.nrm += (size_t) step * A.slot_self; srec.dvec += (size_t) step * A.slot_self;
   srec.meta += (size_t) step * A.slot_meta; srec.verts += (size_t) step * 2 * A.slot_self;
   if constexpr (DETECT) {                     // fused sweeps: detection + layering of this step run here (dc_selflib.h)
-    self_detect_rollout<THREADS>(S, W, b, A.x_in + so, A.v_in + so, A.rec_prim + (size_t) step * A.slot_prim, srec, fu_s, A.fv, fvs_s, pcen_s, pvel_all, (int *) lp, A.fv2);
+    self_detect_rollout<THREADS>(S, W, b, A.x_in + so, A.v_in + so, A.rec_prim + (size_t) step * A.slot_prim, srec, fu_s, A.fv, fvs_s, pcen_s, pvel_all, pshp_all, (int *) lp, A.fv2);
     __syncthreads();
   }
   const float *mu = A.mu + (size_t) b * S.ngroups;
@@ -126,7 +128,7 @@ __device__ __forceinline__ void pd_step_pk(const DevSystem *__restrict__ Sp, con
     part += dot(v0, v0);
     int prim = -1;
     f3 nrm = mk(0, 0, 0);
-    if (S.contact_enabled) prim = detect_primitive(S, pcen_s + (size_t) b * 3 * S.nprim, pvel_s, ld3(xn, i, N), v0, nrm);
+    if (S.contact_enabled) prim = detect_primitive(S, pcen_s + (size_t) b * 3 * S.nprim, pvel_s, pshp_s, ld3(xn, i, N), v0, nrm);
     rec_prim[i] = prim;
     st3(rec_n, i, N, nrm);
     ncontact += (prim >= 0);

@@ -46,6 +46,7 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_res(const DevSystem *__rest
   const float *xfix = A.x_fixed + (size_t) b * 3 * S.Af;
   const float *mu = A.mu + (size_t) b * S.ngroups;
   const float *pvel_b = A.pvel ? A.pvel + (size_t) b * 3 * S.ngroups : nullptr;      // this step's obstacle velocities of this rollout (null: none set)
+  const float *pshp_b = A.pshp ? A.pshp + (size_t) b * 8 * S.nprim : nullptr;        // this step's obstacle shapes of this rollout (null: DevPrim's)
   const float h = S.h;
   const f3 grav = mk(S.gx, S.gy, S.gz);
   const f3 fu = A.fu ? mk(A.fu[3 * b], A.fu[3 * b + 1], A.fu[3 * b + 2]) : mk(0, 0, 0);
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_res(const DevSystem *__rest
     part += dot(v0, v0);
     int prim = -1;
     f3 nrm = mk(0, 0, 0);
-    if (S.contact_enabled) prim = detect_primitive(S, A.pcen + (size_t) b * 3 * S.nprim, pvel_b, ld3(xn, i, N), v0, nrm);
+    if (S.contact_enabled) prim = detect_primitive(S, A.pcen + (size_t) b * 3 * S.nprim, pvel_b, pshp_b, ld3(xn, i, N), v0, nrm);
     rec_prim[i] = prim;
     st3(rec_n, i, N, nrm);
     ncontact += (prim >= 0);

@@ -131,11 +131,12 @@ __device__ int contact_layering_rest(const SelfTmp &t, int nact, int remaining) 
 
 // Detection + layering of one rollout for the step that reads (xn, vn); `lds` = kSelfDetectLdsInts ints of LDS scratch.
 // rec_prim / self / fu / pcen (the step's primitive centres, [B][nprim][3]) / pvel (the step's obstacle velocities, [B][ngroups][3], or null)
+// / pshp (the step's obstacle shapes, [B][nprim][8], or null)
 // are the step's pointers of the whole batch (indexed by b inside).
 // Call with all threads.
 template <int THREADS>
 __device__ __forceinline__ void self_detect_rollout(const DevSystem &S, const DevWork &W, int b, const float *x_in, const float *v_in,
-                                                    int *rec_prim_all, const SelfRec &selfrec, const float *fu_all, const float *fv_all, const float *fvs_all, const float *pcen_all, const float *pvel_all, int *lds, const float *fv2_all = nullptr) {
+                                                    int *rec_prim_all, const SelfRec &selfrec, const float *fu_all, const float *fv_all, const float *fvs_all, const float *pcen_all, const float *pvel_all, const float *pshp_all, int *lds, const float *fv2_all = nullptr) {
   float *redf = (float *) lds;              // [16]
   int *hist = lds + 16;                     // [kSelfCells + 1]
   int *cursor = hist + kSelfCells + 1;      // [kSelfCells]
@@ -187,7 +188,8 @@ __device__ __forceinline__ void self_detect_rollout(const DevSystem &S, const De
     // primitive contacts seed the layering frontier (Simulation.cpp:455-460); the step kernel recomputes the same
     // flags (same inputs — the same row of primitive centres among them —, same code) and also stores the normals
     f3 nrm;
-    rec_prim_all[(size_t) b * N + i] = detect_primitive(S, pcen_all + (size_t) b * 3 * S.nprim, pvel_all ? pvel_all + (size_t) b * 3 * S.ngroups : nullptr, x, v, nrm);
+    rec_prim_all[(size_t) b * N + i] = detect_primitive(S, pcen_all + (size_t) b * 3 * S.nprim, pvel_all ? pvel_all + (size_t) b * 3 * S.ngroups : nullptr,
+                                                        pshp_all ? pshp_all + (size_t) b * 8 * S.nprim : nullptr, x, v, nrm);
   }
   float maxd[3], mind[3];
   for (int d = 0; d < 3; d++) { maxd[d] = block_max<THREADS>(mx[d], redf); mind[d] = -block_max<THREADS>(-mn[d], redf); }

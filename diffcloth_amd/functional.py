@@ -171,16 +171,22 @@ def sim_step(sim, x, v, a):
 _ROLLOUT_INPUTS = ("x0", "v0", "actions", "uniform_force", "vertex_force_scale", "vertex_forces", "mu")
 
 
-def _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets=None, primitive_velocities=None):
+def _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets=None, primitive_velocities=None,
+                   primitive_shapes=None):
     """Checks the arguments of sim_rollout against the engine's sizes and returns the episode length T. Touches no device."""
     e = sim.engine
     B, N, Af, G = e.B, e.N, e.Af, e.ngroups
     given = dict(zip(_ROLLOUT_INPUTS, (x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu)))
     given["primitive_offsets"] = primitive_offsets
     given["primitive_velocities"] = primitive_velocities
+    given["primitive_shapes"] = primitive_shapes
     if torch.is_tensor(primitive_offsets) and primitive_offsets.requires_grad:
         raise ValueError("sim_rollout: primitive_offsets requires grad, but there is no gradient with respect to an obstacle's centre: the adjoint "
                          "holds the contact normals of the record constant, as the reference's does. Pass primitive_offsets.detach()")
+    if torch.is_tensor(primitive_shapes) and primitive_shapes.requires_grad:
+        raise ValueError("sim_rollout: primitive_shapes requires grad, but there is no gradient with respect to an obstacle's shape: the adjoint "
+                         "holds the normals and the contact set of the record constant and does not see an obstacle's shape at all. "
+                         "Pass primitive_shapes.detach()")
     if x0 is None or v0 is None:
         raise ValueError("sim_rollout: x0 and v0 are required")
     for name, t in given.items():
@@ -208,6 +214,8 @@ def _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scal
     for name in ("primitive_offsets", "primitive_velocities"):
         if T is None and given[name] is not None and given[name].dim() == 4:
             T = int(given[name].shape[0])
+    if T is None and primitive_shapes is not None and primitive_shapes.dim() == 4:
+        T = int(primitive_shapes.shape[0])
     if T is None:
         if steps is None:
             raise ValueError("sim_rollout: no schedule given, pass steps=")
@@ -222,6 +230,11 @@ def _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scal
         if name in ("primitive_offsets", "primitive_velocities"):
             if t is not None and tuple(t.shape) not in ((T, B, G, 3), (B, G, 3)):
                 raise ValueError(f"sim_rollout: wrong shape: {name} is {tuple(t.shape)}, expected {(T, B, G, 3)} (one per step) or {(B, G, 3)}")
+        elif name == "primitive_shapes":
+            if t is not None:
+                P = e.nprims       # (read only when the argument is given: an engine without the attribute still runs every other episode)
+                if tuple(t.shape) not in ((T, B, P, 8), (B, P, 8)):
+                    raise ValueError(f"sim_rollout: wrong shape: {name} is {tuple(t.shape)}, expected {(T, B, P, 8)} (one per step) or {(B, P, 8)}")
         elif t is not None and tuple(t.shape) != want[name]:
             raise ValueError(f"sim_rollout: wrong shape: {name} is {tuple(t.shape)}, expected {want[name]}")
     if T > e.tape:
@@ -235,7 +248,8 @@ def _np64(t):
 
 class RolloutFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, sim, T, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets=None, primitive_velocities=None):
+    def forward(ctx, sim, T, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets=None, primitive_velocities=None,
+                primitive_shapes=None):
         e = sim.engine
         B, N = e.B, e.N
         if primitive_offsets is not None and primitive_offsets.dim() == 3:      # constant over the episode: the same entry in every step
@@ -243,6 +257,8 @@ class RolloutFunction(torch.autograd.Function):
         ctx.velocities_per_episode = primitive_velocities is not None and primitive_velocities.dim() == 3      # (its gradient: summed over the steps)
         if ctx.velocities_per_episode:
             primitive_velocities = primitive_velocities.detach().unsqueeze(0).expand(T, *primitive_velocities.shape)
+        if primitive_shapes is not None and primitive_shapes.dim() == 3:
+            primitive_shapes = primitive_shapes.detach().unsqueeze(0).expand(T, *primitive_shapes.shape)
         sim._episode += 1
         ctx.sim, ctx.T, ctx.episode = sim, T, sim._episode
         ctx.save_for_backward(vertex_forces, vertex_force_scale)
@@ -265,6 +281,8 @@ class RolloutFunction(torch.autograd.Function):
                 e.set_primitive_offset_schedule_dev(0, T, primitive_offsets.detach())
             if primitive_velocities is not None:
                 e.set_primitive_velocity_schedule_dev(0, T, primitive_velocities.detach())
+            if primitive_shapes is not None:
+                e.set_primitive_shape_schedule_dev(0, T, primitive_shapes.detach())
             e.rollout_forward_async(0, T)
             xs = torch.empty((T, B, 3 * N), dtype=x0.dtype, device=x0.device)
             vs = torch.empty_like(xs)
@@ -286,6 +304,8 @@ class RolloutFunction(torch.autograd.Function):
             e.set_primitive_offset_schedule(0, _np64(primitive_offsets))
         if primitive_velocities is not None:
             e.set_primitive_velocity_schedule(0, _np64(primitive_velocities))
+        if primitive_shapes is not None:
+            e.set_primitive_shape_schedule(0, _np64(primitive_shapes))
         e.rollout_forward(0, T)
         xs, vs = e.get_states(1, T)
         sim.step_idx = T
@@ -334,7 +354,7 @@ class RolloutFunction(torch.autograd.Function):
                 if ctx.velocities_per_episode:
                     dw = dw.sum(0)
             sim.check_episode()                # the single synchronisation of the episode: errors of both sweeps surface here
-            return None, None, dx0, dv0, da, dfu, dfvs, dfv, dmu, None, dw
+            return None, None, dx0, dv0, da, dfu, dfvs, dfv, dmu, None, dw, None
         gxs, gvs = _np64(grad_xs), _np64(grad_vs)
         e.keep_force_gradients(keep)
         zero = np.zeros((1, B, 3 * N))
@@ -358,17 +378,17 @@ class RolloutFunction(torch.autograd.Function):
             dw = e.get_primitive_velocity_gradients(1, T)
             dw = t(dw.sum(0) if ctx.velocities_per_episode else dw)
         sim.check_episode()
-        return None, None, t(dx0), t(dv0), da, dfu, dfvs, dfv, (t(dmu) if need_mu else None), None, dw
+        return None, None, t(dx0), t(dv0), da, dfu, dfvs, dfv, (t(dmu) if need_mu else None), None, dw, None
 
 
 def sim_rollout(sim, x0, v0, actions=None, *, steps=None, uniform_force=None, vertex_force_scale=None, vertex_forces=None, mu=None,
-                primitive_offsets=None, primitive_velocities=None):
+                primitive_offsets=None, primitive_velocities=None, primitive_shapes=None):
     """A whole differentiable episode of all rollouts: the states after every step, (xs, vs), [T, B, 3N] each in the dtype of x0.
 
     x0, v0: [B, 3N] initial state. actions: [T, B, 3 Af] clip targets of every step. uniform_force: [T, B, 3] force on every vertex per
     step. vertex_forces: [B, 3N] per-vertex force field, vertex_force_scale: [T, B] its factor per step (1 when omitted; the field is the
     factor-free one). mu: [B, G] friction coefficient per primitive group. T comes from the first schedule given, or from `steps`.
-    Gradients flow to every tensor argument that requires one, except primitive_offsets.
+    Gradients flow to every tensor argument that requires one, except primitive_offsets and primitive_shapes.
 
     primitive_offsets: [T, B, G, 3] offset of every primitive group's centre per step and rollout, or [B, G, 3] for the whole episode
     (Engine.set_primitive_offset_schedule: the obstacle of group g is tested at fp32(center + offset)). When omitted the schedule is cleared
@@ -383,6 +403,13 @@ def sim_rollout(sim, x0, v0, actions=None, *, steps=None, uniform_force=None, ve
     moves an obstacle along c(t) passes offsets[s] = c(t_s) - c_built and velocities[s] = (c(t_{s+1}) - c(t_s)) / h — the offset is the
     obstacle's position at the start of step s, and it moves by velocities[s] h during the step.
 
+    primitive_shapes: [T, B, P, 8] shape row {top_offset[3], corner2[3], radius, length} of every flattened primitive (Engine.set_primitives
+    order) per step and rollout, or [B, P, 8] for the whole episode (Engine.set_primitive_shape_schedule: the kernels read fp32 of these
+    numbers in place of the built ones; Engine.built_primitive_shapes() gives the built rows and rotated_primitive_shapes tilts them). When
+    omitted the schedule is cleared like the others and the engine's current shapes (Engine.set_primitive_shapes; the built ones by
+    default) apply. A tensor that requires grad is refused: the adjoint does not see an obstacle's shape. A shape schedule alone leaves
+    the surface static in the friction law; the translation part of a swinging obstacle's motion goes into primitive_velocities.
+
     The episode occupies tape slots 0 .. T (T <= the tape of alloc_batch) and replaces what the tape held: the function sets the trajectory
     start to slot 0, clears the schedules it does not set, and leaves sim.step_idx = T. `mu` and `vertex_forces`, when given, stay set on
     the engine as after Engine.set_mu / set_vertex_forces; when omitted the engine's current values apply, as does its current uniform
@@ -395,6 +422,24 @@ def sim_rollout(sim, x0, v0, actions=None, *, steps=None, uniform_force=None, ve
 
     The action gradient is dL_dxfixed of every step as the adjoint gives it: it is NOT rescaled. The clamp of its norm belongs to
     `sim_step`, which mirrors the reference's per-step function (functional.py:88-97)."""
-    T = _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets, primitive_velocities)
+    T = _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets, primitive_velocities,
+                       primitive_shapes)
     return RolloutFunction.apply(sim, T, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets,
-                                 primitive_velocities)
+                                 primitive_velocities, primitive_shapes)
+
+
+def rotated_primitive_shapes(shapes, R):
+    """Shape rows with their vectors rotated: shapes [..., P, 8] = {top_offset[3], corner2[3], radius, length} per flattened primitive, R
+    [..., P, 3, 3] rotation matrices (leading dimensions broadcast). Returns rows of the broadcast shape with top_offset and corner2
+    replaced by R top_offset and R corner2, computed in the tensors' dtype, radius and length kept. This is how a caller tilts a plane or
+    swings a capsule about its centre with sim_rollout(primitive_shapes=...) / Engine.set_primitive_shapes: the kernels do no rotation
+    arithmetic, they read the rotated vectors."""
+    shapes, R = torch.as_tensor(shapes), torch.as_tensor(R)
+    if shapes.shape[-1] != 8 or R.shape[-2:] != (3, 3):
+        raise ValueError(f"rotated_primitive_shapes: shapes [..., P, 8] and R [..., P, 3, 3], got {tuple(shapes.shape)} and {tuple(R.shape)}")
+    R = R.to(shapes.dtype)
+    lead = torch.broadcast_shapes(shapes.shape[:-1], R.shape[:-2])
+    shapes = shapes.expand(*lead, 8)
+    top = (R @ shapes[..., 0:3].unsqueeze(-1)).squeeze(-1)
+    ur = (R @ shapes[..., 3:6].unsqueeze(-1)).squeeze(-1)
+    return torch.cat([top, ur, shapes[..., 6:8]], dim=-1)

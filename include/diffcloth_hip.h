@@ -388,6 +388,38 @@ int dc_set_primitive_velocity_schedule_dev(dc_ctx *ctx, int slot0, int nsteps, c
 int dc_get_primitive_velocities(dc_ctx *ctx, int slot, double *w /*B*G*3*/);
 int dc_get_primitive_velocity_gradients(dc_ctx *ctx, int slot0, int nslots, double *dL_dw /*nslots*B*G*3*/);
 int dc_get_primitive_velocity_gradients_dev(dc_ctx *ctx, int slot0, int nslots, void *d_dL_dw /*nslots*B*G*3*/, int is_f32);
+/* ---- obstacle shapes per rollout and step: radius, capsule axis and length, the two corners of a finite plane. ONE rule, next to the two above:
+ * a SHAPE ROW of 8 numbers per rollout b and FLATTENED primitive p (dc_set_primitives order, P <= 8; per primitive, not per group: the children
+ * of a LowerLeg each have their own), the dc_primitive fields of the same names,
+ *         s[b][p] = {top_offset[3], corner2[3], radius, length}
+ * and the device stores fp32(value), each value rounded once — what dc_build does when it fills its primitive table (one conversion,
+ * csrc/dc_primshape.h, called by both). The kernels do no rotation arithmetic: they read the eight numbers of the step's row in place of the
+ * built ones, so a context GIVEN a shape and a context BUILT with that shape compute the same step bit for bit. A caller who tilts a plane or
+ * swings a capsule about its centre rotates top_offset and corner2 and passes the result. kind, group, mu, rotates and the centre stay what they
+ * are (the centre has its own entries above; a capsule's centre is its lower end, so swinging it about its middle needs both). The bowl's "below
+ * the centre" test stays world-up. For a DC_PRIM_SPHERE_DISCRETIZED the kernels do NOT read the row — its face table is built for one radius —
+ * and the host setters refuse (DC_ERR_INVALID) a row for it that differs from the built one after rounding.
+ * A shape schedule alone leaves the surface STATIC in the friction law, as an offset alone does: the surface velocity of a rotating or growing
+ * obstacle is not modelled. A caller who wants the translation part passes velocities (dc_set_primitive_velocities). There is no gradient with
+ * respect to a shape: the adjoint holds the record's normals and contact set constant and does not read the shape at all.
+ * Storage: a table [slot][B][P][8] in fp32 and a current set [B][P][8], allocated by the first of these setters after dc_alloc_batch and filled
+ * with the built shapes; until then the kernels read the built primitive table (a null pointer: one uniform branch). Row `slot` is what the step
+ * that PRODUCED `slot` used.
+ * dc_set_primitive_shapes: shapes of the NEXT forward steps without a schedule entry (s = B*P*8; NULL = the built shapes).
+ * dc_set_primitive_shape_schedule: the step slot0 + k -> slot0 + k + 1 uses s[k]. The rules of the offset and velocity entries hold throughout:
+ * an entry stays until it is overwritten, dc_clear_schedules or dc_alloc_batch; the per-step calls honour it; a fused sweep needs it on all of
+ * its steps or on none (DC_ERR_INVALID); dc_alloc_batch, dc_set_primitives and dc_build drop everything; a host-only context answers
+ * DC_ERR_STATE; P == 0 gives DC_ERR_INVALID. The host forms refuse non-finite values (DC_ERR_INVALID). The _dev forms take DEVICE pointers (fp32
+ * or fp64) on the context's stream — one launch for all slots, no synchronisation — and so cannot look at the values: a degenerate shape (a
+ * zero-length capsule axis, collinear plane corners, a non-finite number, another radius for a discretised sphere's unread row) gives what a
+ * context built with it would give.
+ * dc_get_primitive_shapes: the fp32 rows, widened, that the step which produced `slot` used (B*P*8; the built shapes when none was ever set).
+ * Synchronises.                                                                                                                             */
+int dc_set_primitive_shapes(dc_ctx *ctx, const double *s /*B*P*8 or NULL = the built shapes*/);
+int dc_set_primitive_shape_schedule(dc_ctx *ctx, int slot0, int nsteps, const double *s /*nsteps*B*P*8*/);
+int dc_set_primitive_shapes_dev(dc_ctx *ctx, const void *d_s /*B*P*8 or NULL*/, int is_f32);
+int dc_set_primitive_shape_schedule_dev(dc_ctx *ctx, int slot0, int nsteps, const void *d_s /*nsteps*B*P*8*/, int is_f32);
+int dc_get_primitive_shapes(dc_ctx *ctx, int slot, double *s /*B*P*8*/);
 /* states of nslots consecutive slots in one call: x[k*B*3N ...], v likewise (either may be NULL) */
 int dc_get_states(dc_ctx *ctx, int slot0, int nslots, double *x, double *v);
 /* dL_dxfixed of the steps through records slot0 .. slot0+nslots-1 of the last backward sweep / step (B*3Af each) */
