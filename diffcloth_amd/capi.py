@@ -69,6 +69,8 @@ EXPORTED_SYMBOLS = [
     "dc_get_primitive_centers",
     "dc_set_primitive_velocities", "dc_set_primitive_velocity_schedule", "dc_set_primitive_velocities_dev", "dc_set_primitive_velocity_schedule_dev",
     "dc_get_primitive_velocities", "dc_get_primitive_velocity_gradients", "dc_get_primitive_velocity_gradients_dev",
+    "dc_set_primitive_spins", "dc_set_primitive_spin_schedule", "dc_set_primitive_spins_dev", "dc_set_primitive_spin_schedule_dev",
+    "dc_get_primitive_spins", "dc_get_primitive_spin_gradients", "dc_get_primitive_spin_gradients_dev",
     "dc_set_primitive_shapes", "dc_set_primitive_shape_schedule", "dc_set_primitive_shapes_dev", "dc_set_primitive_shape_schedule_dev",
     "dc_get_primitive_shapes",
 ]
@@ -318,6 +320,29 @@ class Engine:
         """[B][P][8] shape rows that the step which produced `slot` used (fp32 values, widened; the built shapes when none was ever set)"""
         out = np.zeros((self.B, self.nprims, 8))
         self._chk(self.lib.dc_get_primitive_shapes(self.h, C.c_int(slot), _d(out)))
+        return out
+
+    def set_primitive_spins(self, omega):
+        """omega: [B][G][3] angular velocities (rad/s) of the primitive groups for the NEXT forward steps (dc_set_primitive_spins: a DC_PRIM_SPHERE
+        adds v_spin = radius (omega x n) to the v_out of the friction law; stored as fp32); None = zeros"""
+        a = None if omega is None else self._vec(omega, 3 * self.ngroups)
+        self._chk(self.lib.dc_set_primitive_spins(self.h, _d(a)))
+
+    def set_primitive_spin_schedule(self, slot0, omega):
+        """omega: [nsteps][B][G][3]: the step slot0+k -> slot0+k+1 uses omega[k] (dc_set_primitive_spin_schedule)"""
+        omega = np.ascontiguousarray(np.asarray(omega, dtype=np.float64).reshape(-1, self.B, self.ngroups, 3))
+        self._chk(self.lib.dc_set_primitive_spin_schedule(self.h, C.c_int(slot0), C.c_int(omega.shape[0]), _d(omega)))
+
+    def get_primitive_spins(self, slot):
+        """[B][G][3] angular velocities that the step which produced `slot` used (fp32 values, widened; zeros when none was ever set)"""
+        out = np.zeros((self.B, self.ngroups, 3))
+        self._chk(self.lib.dc_get_primitive_spins(self.h, C.c_int(slot), _d(out)))
+        return out
+
+    def get_primitive_spin_gradients(self, slot0, nslots):
+        """[nslots][B][G][3] dL/domega of the backward steps through records slot0 .. slot0+nslots-1 (dc_get_primitive_spin_gradients)"""
+        out = np.zeros((nslots, self.B, self.ngroups, 3))
+        self._chk(self.lib.dc_get_primitive_spin_gradients(self.h, C.c_int(slot0), C.c_int(nslots), _d(out)))
         return out
 
     def get_force_gradient(self):
@@ -571,6 +596,23 @@ class Engine:
         """dL/dw of the backward steps through records slot0 .. slot0+nslots-1 into a contiguous CUDA tensor [nslots][B][G][3]"""
         (p,), f = self._tps((dw, self.B * self.ngroups * 3, nslots))
         self._chk(self.lib.dc_get_primitive_velocity_gradients_dev(self.h, C.c_int(slot0), C.c_int(nslots), p, C.c_int(f)))
+
+    def set_primitive_spins_dev(self, omega):
+        """dc_set_primitive_spins from a CUDA tensor [B][G][3] (a non-contiguous view is copied first); None = zeros"""
+        self._spins_dev = omega = None if omega is None else omega.contiguous()      # (kept alive until the next call: the conversion is only enqueued)
+        (p,), f = self._tps((omega, self.B * self.ngroups * 3, 1))
+        self._chk(self.lib.dc_set_primitive_spins_dev(self.h, p, C.c_int(f)))
+
+    def set_primitive_spin_schedule_dev(self, slot0, nsteps, omega):
+        """dc_set_primitive_spin_schedule from a CUDA tensor [nsteps][B][G][3] (a non-contiguous view is copied first)"""
+        self._spin_schedule_dev = omega = omega.contiguous()
+        (p,), f = self._tps((omega, self.B * self.ngroups * 3, nsteps))
+        self._chk(self.lib.dc_set_primitive_spin_schedule_dev(self.h, C.c_int(slot0), C.c_int(nsteps), p, C.c_int(f)))
+
+    def get_primitive_spin_gradients_dev(self, slot0, nslots, dw):
+        """dL/domega of the backward steps through records slot0 .. slot0+nslots-1 into a contiguous CUDA tensor [nslots][B][G][3]"""
+        (p,), f = self._tps((dw, self.B * self.ngroups * 3, nslots))
+        self._chk(self.lib.dc_get_primitive_spin_gradients_dev(self.h, C.c_int(slot0), C.c_int(nslots), p, C.c_int(f)))
 
     # ---- device-resident schedules (dc_set_*_schedule) ----
     def set_gradient(self, dL_dx, dL_dv):

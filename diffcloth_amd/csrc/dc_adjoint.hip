@@ -122,7 +122,7 @@ __device__ __forceinline__ void krylov_sum2(float a, float b, double *slot, doub
 struct AdjCtx {
   const float *xnew, *rec_f, *rec_n, *mu;
 #ifdef DC_ADJ_VELOCITY
-  const float *pvel;            // [ngroups][3] obstacle velocities of the record's step, this rollout (prim_d)
+  const float *pvel;            // [ngroups][kPvRow] obstacle motion {w, omega} of the record's step, this rollout (prim_d)
 #endif
   const int *rec_prim;
   float *y, *corner, *lds;
@@ -730,7 +730,7 @@ __global__ __launch_bounds__(THREADS) void k_adjoint_step(const DevSystem *__res
   C.rec_prim = A.rec_prim + (size_t) b * N;
   C.mu = A.mu + (size_t) b * S.ngroups;
 #ifdef DC_ADJ_VELOCITY
-  C.pvel = A.pvel + (size_t) b * 3 * S.ngroups;      // obstacle velocities of the record's step, this rollout
+  C.pvel = A.pvel + (size_t) b * kPvRow * S.ngroups;      // obstacle velocities of the record's step, this rollout
 #endif
   C.y = W.vbest + off; C.corner = W.corner + (size_t) b * 3 * S.NC;
   C.self = A.self; C.b = b;
@@ -858,7 +858,7 @@ __global__ __launch_bounds__(THREADS) void k_adjoint_step(const DevSystem *__res
   C64.xprev = A.x_prev + off; C64.vnew = A.v_new + off;
   C64.xnew = C.xnew; C64.rec_f = C.rec_f; C64.rec_n = C.rec_n; C64.mu = C.mu; C64.rec_prim = C.rec_prim;
 #ifdef DC_ADJ_VELOCITY
-  C64.pvel = C.pvel; C64.d_pvel = A.d_pvel + (size_t) b * 3 * S.ngroups;
+  C64.pvel = C.pvel; C64.d_pvel = A.d_pvel + (size_t) b * kPvRow * S.ngroups;
 #endif
   C64.self = C.self; C64.nself = C.nself; C64.b = b; C64.lds = dyn_lds; C64.lds_floats = C.lds_floats;
   adj64_inject(C64, A, b, N, S.self_cap);

@@ -75,8 +75,8 @@ struct Work64 {
 struct Adj64 {
   const float *xnew, *rec_f, *rec_n, *mu;
 #ifdef DC_ADJ_VELOCITY
-  const float *pvel;                        // [ngroups][3] obstacle velocities of the record's step, this rollout; null = none set
-  float *d_pvel;                            // [ngroups][3] dL/dw of this step, this rollout (finish_gradients64 writes it); null = none set
+  const float *pvel;                        // [ngroups][kPvRow] obstacle motion {w, omega} of the record's step, this rollout; null = none set
+  float *d_pvel;                            // [ngroups][kPvRow] {dL/dw, dL/domega} of this step, this rollout (finish_gradients64 writes it); null = none set
 #endif
   const float *xprev, *vnew;                // state the step started from, velocity it ended with (tape slots k - 1 and k)
   const int *rec_prim;
@@ -210,12 +210,15 @@ __device__ __forceinline__ d3 dri_dmu_dd(d3 n, d3 d, double mu) {
 __device__ __forceinline__ d3 prim_vout_d(const DevPrim &p, d3 n) {
   return p.rotates ? cross(mkd(0, 1, 0), n) * 8.0 : mkd(0, 0, 0);   // Primitive.cpp:254-257
 }
-// prim_d (dc_devlib.h) on a record handed in from outside: d = (f - v_rot m) - w m in fp64, w = (double) fp32(w) as the device stores it
+// prim_d (dc_devlib.h) on a record handed in from outside: d = ((f - v_rot m) - w m) - v_spin m in fp64, w and omega = (double) fp32(.) as the
+// device stores them, v_spin = radius (omega x n) for a DC_PRIM_SPHERE whose group's stored omega is not all +-0
 __device__ __forceinline__ d3 prim_d_d(const DevPrim &p, d3 n, d3 f, double m, const float *wv) {
   d3 d = f - prim_vout_d(p, n) * m;
   if (wv) {
-    const float DC_G *w = (const float DC_G *) wv + 3 * p.group;
+    const float DC_G *w = (const float DC_G *) wv + kPvRow * p.group;
     d = d - mkd((double) w[0], (double) w[1], (double) w[2]) * m;
+    if (p.kind == DC_PRIM_SPHERE && (w[3] != 0.f || w[4] != 0.f || w[5] != 0.f))
+      d = d - (cross(mkd((double) w[3], (double) w[4], (double) w[5]), n) * (double) p.radius) * m;
   }
   return d;
 }
@@ -778,16 +781,26 @@ __device__ DC_OUTLINED Ret64<Team> finish_gradients64(const DevSystem &S, Adj64 
   if (C.d_pvel) {
     // dL/dw[g] = -h sum over the vertices i in contact with group g of m_i (dr_i/dd_i)^T u_i (dd_i/dw = -m_i I; the convention of dL_dmu: normals
     // and contact set held constant), one pass over the own rows per group — only contexts that were ever given a velocity come here
+    // dL/domega[g] = -h sum over the contacts with a DC_PRIM_SPHERE p of group g of m_i radius_p (n_i x g_i), g_i = (dr_i/dd_i)^T u_i
+    // (dd_i/domega . e = -m_i radius_p (e x n_i)): the same pass, a second reduction. Row g of the table is {dL/dw[3], dL/domega[3]}.
     float *dw = C.d_pvel;
     for (int g = 0; g < S.ngroups; g++) {
-      d3 acc = mkd(0, 0, 0);
+      d3 acc = mkd(0, 0, 0), spin = mkd(0, 0, 0);
       for (int i = tm.r0() + tid; i < tm.r1(); i += THREADS) {
         const int prim = C.rec_prim[i];
-        if (prim >= 0 && S.prims[prim].group == g) acc = acc + contact_JT_d(S, C, i, ld3d(W.u, i, N)) * S.mass64[i];
+        if (prim >= 0 && S.prims[prim].group == g) {
+          const d3 gi = contact_JT_d(S, C, i, ld3d(W.u, i, N)) * S.mass64[i];
+          acc = acc + gi;
+          if (S.prims[prim].kind == DC_PRIM_SPHERE)
+            spin = spin + cross(C.inj_f ? ld3d(C.inj_n, i, N) : tod(ld3(C.rec_n, i, N)), gi) * (double) S.prims[prim].radius;
+        }
       }
       if (!tm.sum3(acc.x, acc.y, acc.z, s3)) return ret(-1);
       if (writer)
-        for (int c = 0; c < 3; c++) dw[3 * g + c] = (float) (-h * s3[c]);
+        for (int c = 0; c < 3; c++) dw[kPvRow * g + c] = (float) (-h * s3[c]);
+      if (!tm.sum3(spin.x, spin.y, spin.z, s3)) return ret(-1);
+      if (writer)
+        for (int c = 0; c < 3; c++) dw[kPvRow * g + 3 + c] = (float) (-h * s3[c]);
     }
   }
 #endif

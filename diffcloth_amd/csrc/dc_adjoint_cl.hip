@@ -111,7 +111,7 @@ namespace {
 struct AdjCl {
   const float *xnew, *rec_f, *rec_n, *mu;
 #ifdef DC_ADJ_VELOCITY
-  const float *pvel;            // [ngroups][3] obstacle velocities of the record's step, this rollout (prim_d)
+  const float *pvel;            // [ngroups][kPvRow] obstacle motion {w, omega} of the record's step, this rollout (prim_d)
 #endif
   const int *rec_prim;
   BufVec yb;                    // y = (I + dr_df)^T z of the rollout, read across parts: write-through stores, L1-bypassing loads
@@ -253,7 +253,7 @@ __global__ __launch_bounds__(THREADS) void DC_ADJ_CL_KERNEL(const DevSystem *__r
   C.rec_prim = A.rec_prim + (size_t) b * N;
   C.mu = A.mu + (size_t) b * S.ngroups;
 #ifdef DC_ADJ_VELOCITY
-  C.pvel = A.pvel + (size_t) b * 3 * S.ngroups;      // obstacle velocities of the record's step, this rollout
+  C.pvel = A.pvel + (size_t) b * kPvRow * S.ngroups;      // obstacle velocities of the record's step, this rollout
 #endif
   C.yb = buf_vec(W.vbest + off, N, X.same_xcd);
   C.self = A.self; C.b = b; C.part = part; C.r0 = r0; C.r1 = r1; C.R = R; C.HB = HB;
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(THREADS) void DC_ADJ_CL_KERNEL(const DevSystem *__r
   C64.xprev = A.x_prev + off; C64.vnew = A.v_new + off;
   C64.xnew = C.xnew; C64.rec_f = C.rec_f; C64.rec_n = C.rec_n; C64.mu = C.mu; C64.rec_prim = C.rec_prim;
 #ifdef DC_ADJ_VELOCITY
-  C64.pvel = C.pvel; C64.d_pvel = A.d_pvel + (size_t) b * 3 * S.ngroups;
+  C64.pvel = C.pvel; C64.d_pvel = A.d_pvel + (size_t) b * kPvRow * S.ngroups;
 #endif
   C64.self = C.self; C64.nself = C.nself; C64.b = b; C64.lds = dyn_lds; C64.lds_floats = hc_off;
   adj64_inject(C64, A, b, N, S.self_cap);

@@ -14,8 +14,8 @@ __device__ __forceinline__ Adj64 dense_adj64(const DevSystem &S, const BwdArgs &
   Adj64 C;
   C.xnew = A.x_new + off; C.rec_f = A.rec_f + off; C.rec_n = A.rec_n + off;
   C.mu = A.mu + (size_t) b * S.ngroups;
-  C.pvel = A.pvel ? A.pvel + (size_t) b * 3 * S.ngroups : nullptr;      // obstacle velocities of the record's step (null: none set)
-  C.d_pvel = A.d_pvel ? A.d_pvel + (size_t) b * 3 * S.ngroups : nullptr;
+  C.pvel = A.pvel ? A.pvel + (size_t) b * kPvRow * S.ngroups : nullptr;      // obstacle velocities of the record's step (null: none set)
+  C.d_pvel = A.d_pvel ? A.d_pvel + (size_t) b * kPvRow * S.ngroups : nullptr;
   C.xprev = A.x_prev + off; C.vnew = A.v_new + off;
   C.rec_prim = A.rec_prim + (size_t) b * N;
   C.self = A.self; C.b = b;

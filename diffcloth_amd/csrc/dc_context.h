@@ -82,13 +82,16 @@ struct dc_ctx {
   std::vector<int> pc_row_gen;
   int pc_gen = 0, pc_gen_last = 0;
   std::vector<char> sched_pc;
-  // obstacle velocities (dc_set_primitive_velocities / dc_set_primitive_velocity_schedule): fp32, per primitive GROUP. All three arrays are
-  // allocated by the first velocity setter after dc_alloc_batch and zeroed; while PV is null the kernels get null pointers and evaluate the
-  // static contact law. Row `slot` of PV is what the step that produced `slot` used and what the backward step through record `slot` reads.
-  float *PV = nullptr;              // [(tape+1)][B][G][3]
-  float *pv_cur = nullptr;          // [B][G][3] velocities of the NEXT steps that have no schedule entry
-  float *DPV = nullptr;             // [(tape+1)][B][G][3] dL/dw of the backward step through record `slot` (overwritten per step)
-  std::vector<char> sched_pv;
+  // obstacle motion: velocities w (dc_set_primitive_velocities / dc_set_primitive_velocity_schedule) and angular velocities omega
+  // (dc_set_primitive_spins / dc_set_primitive_spin_schedule), fp32, one row {w[3], omega[3]} (dc::kPvRow floats) per primitive GROUP. All three
+  // arrays are allocated by the first setter of either kind after dc_alloc_batch and zeroed; while PV is null the kernels get null pointers and
+  // evaluate the static contact law. Row `slot` of PV is what the step that produced `slot` used and what the backward step through record
+  // `slot` reads. The two halves of a row are set, scheduled and read independently (sched_pv: w, sched_pw: omega).
+  float *PV = nullptr;              // [(tape+1)][B][G][6]
+  float *pv_cur = nullptr;          // [B][G][6] motion of the NEXT steps; a half applies where that half has no schedule entry
+  float *DPV = nullptr;             // [(tape+1)][B][G][6] {dL/dw, dL/domega} of the backward step through record `slot` (overwritten per step)
+  std::vector<char> sched_pv, sched_pw;
+  bool pv_set = false, pw_set = false;      // a velocity / a spin setter has run on this batch (the gradient getters of a kind fail before)
   // obstacle shapes (dc_set_primitive_shapes / dc_set_primitive_shape_schedule, dc_primshape.h): fp32 rows {top_offset, corner2, radius, length}
   // per flattened primitive. Allocated by the first shape setter after dc_alloc_batch and filled with the built shapes; while PS is null the
   // kernels get a null pointer and read DevPrim. Row `slot` of PS is what the step that produced `slot` used.

@@ -60,6 +60,17 @@ __global__ void k_copy_cast(const float *__restrict__ src, T *__restrict__ dst, 
   long t = (long) blockIdx.x * blockDim.x + threadIdx.x;
   if (t < total) dst[t] = (T) src[t];
 }
+// one half of the obstacle-motion rows {w[3], omega[3]} (kPvRow floats per rollout and group) <-> the caller's dense [rows][3]
+template <class T>
+__global__ void k_cast_in_half(const T *__restrict__ src, float *__restrict__ dst, long total, int half) {
+  long t = (long) blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < total) dst[(t / 3) * kPvRow + 3 * half + (t % 3)] = (float) src[t];
+}
+template <class T>
+__global__ void k_copy_cast_half(const float *__restrict__ src, T *__restrict__ dst, long total, int half) {
+  long t = (long) blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < total) dst[t] = (T) src[(t / 3) * kPvRow + 3 * half + (t % 3)];
+}
 
 __global__ void k_seed_gradient(const float *__restrict__ x, const float *__restrict__ target, float *__restrict__ gx,
                                 float *__restrict__ gv, int n3, long total, float scale) {
@@ -101,6 +112,18 @@ void launch_copy_cast(const float *src, void *dst, int is_f32, long total, hipSt
   if (total == 0) return;
   if (is_f32) hipLaunchKernelGGL(k_copy_cast<float>, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, st, src, (float *) dst, total);
   else hipLaunchKernelGGL(k_copy_cast<double>, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, st, src, (double *) dst, total);
+}
+void launch_cast_in_half(const void *src, int is_f32, float *dst, long rows, int half, hipStream_t st) {
+  const long total = rows * 3;
+  if (total == 0) return;
+  if (is_f32) hipLaunchKernelGGL(k_cast_in_half<float>, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, st, (const float *) src, dst, total, half);
+  else hipLaunchKernelGGL(k_cast_in_half<double>, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, st, (const double *) src, dst, total, half);
+}
+void launch_copy_cast_half(const float *src, void *dst, int is_f32, long rows, int half, hipStream_t st) {
+  const long total = rows * 3;
+  if (total == 0) return;
+  if (is_f32) hipLaunchKernelGGL(k_copy_cast_half<float>, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, st, src, (float *) dst, total, half);
+  else hipLaunchKernelGGL(k_copy_cast_half<double>, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, st, src, (double *) dst, total, half);
 }
 void launch_seed_gradient(const float *x, const float *target, float *gx, float *gv, int B, int N, float scale, hipStream_t st) {
   long total = (long) B * 3 * N;

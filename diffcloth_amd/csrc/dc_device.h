@@ -28,6 +28,9 @@ constexpr int kMetaStride = 4096;
 #define DC_C
 #endif
 
+// floats per primitive group in a row of the obstacle-motion table (FwdArgs::pvel, BwdArgs::pvel / d_pvel): {w[3], omega[3]}
+constexpr int kPvRow = 6;
+
 struct DevPrim {
   int kind, group, rotates, pad;
   float cx, cy, cz, radius;
@@ -193,8 +196,9 @@ struct FwdArgs {
   // when none are set): a row of the per-slot table, so a fused sweep always steps by slot_pcen = B * nprim * 3
   const float *pcen;
   size_t slot_pcen;
-  // fp32 velocities of the primitive groups in this step, [B][ngroups][3] (dc_set_primitive_velocities / ..._schedule), a row of the per-slot
-  // table stepped by slot_pvel = B * ngroups * 3; NULL until a velocity is set for the first time: the kernels then evaluate the static law
+  // fp32 motion rows {w[3], omega[3]} of the primitive groups in this step, [B][ngroups][kPvRow]: the velocity (dc_set_primitive_velocities /
+  // ..._schedule) and the angular velocity (dc_set_primitive_spins / ..._schedule), a row of the per-slot table stepped by
+  // slot_pvel = B * ngroups * kPvRow; NULL until either is set for the first time: the kernels then evaluate the static law
   const float *pvel;
   size_t slot_pvel;
   // fp32 shape rows {top_offset[3], corner2[3], radius, length} of the flattened primitives in this step, [B][nprim][8] (dc_set_primitive_shapes /
@@ -243,8 +247,9 @@ struct BwdArgsStatic {
 };
 
 struct BwdArgs : BwdArgsStatic {
-  // obstacle velocities the step that produced record k used, [B][ngroups][3] (row k of the table FwdArgs::pvel points into), and dL/dw of this
-  // step, same shape, overwritten (finish_gradients64); both step by slot_pvel, both null until a velocity is set for the first time
+  // obstacle motion rows {w[3], omega[3]} the step that produced record k used, [B][ngroups][kPvRow] (row k of the table FwdArgs::pvel points
+  // into), and {dL/dw[3], dL/domega[3]} of this step, same shape, overwritten (finish_gradients64); both step by slot_pvel, both null until a
+  // velocity or a spin is set for the first time
   const float *pvel;
   float *d_pvel;
   size_t slot_pvel;
@@ -270,6 +275,9 @@ void launch_seed_gradient(const float *x, const float *target, float *gx, float 
 void launch_rows_to_planar(const void *src, int is_f32, float *dst, long rows, int n, const int *user_of, hipStream_t st);
 void launch_planar_to_rows(const float *src, void *dst, int is_f32, long rows, int n, const int *user_of, hipStream_t st);
 void launch_cast_in(const void *src, int is_f32, float *dst, long total, hipStream_t st);
+// one half ({w} = 0, {omega} = 1) of `rows` obstacle-motion rows <-> the caller's dense [rows][3] (fp32 or fp64), one launch
+void launch_cast_in_half(const void *src, int is_f32, float *dst, long rows, int half, hipStream_t st);
+void launch_copy_cast_half(const float *src, void *dst, int is_f32, long rows, int half, hipStream_t st);
 // primitive centres of `rows` = slots x rollouts from per-group offsets (dc_primoffset.h: fp64 sum, one rounding); d null = zero offsets
 void launch_prim_centres(const double *built, const int *group_of_prim, const void *d, int is_f32, float *dst, long rows, int P, int G, hipStream_t st);
 void launch_dfu_from_param(const float *dpar, void *out, int is_f32, long rows, hipStream_t st);

@@ -219,8 +219,9 @@ __device__ __attribute__((noinline)) void sphere_mesh_normal(const DevSystem &S,
 // cen: the absolute fp32 centres [nprim][3] of THIS rollout in THIS step (a row of the table FwdArgs::pcen points into; the built centres
 // when no offsets are set). Every caller of one step passes the same row: the detection that seeds the self-contact layering
 // (dc_selflib.h) and the step kernel must see the same obstacle.
-// wv: the velocities [ngroups][3] of THIS rollout's primitive groups in THIS step (a row of the table FwdArgs::pvel points into), or null
-// when no velocity was ever set. cen is the obstacle's position at the START of the step and the obstacle moves by w h during it: the
+// wv: the motion rows [ngroups][kPvRow] = {w[3], omega[3]} of THIS rollout's primitive groups in THIS step (a row of the table FwdArgs::pvel
+// points into), or null when neither a velocity nor a spin was ever set. Detection reads w alone (a sphere spinning about its centre occupies
+// the same space). cen is the obstacle's position at the START of the step and the obstacle moves by w h during it: the
 // samples of group g are pos + (vel - w[g]) h k / 2, the look-ahead in the obstacle's frame (w = +0 gives vel - 0 = vel bit for bit).
 // Like cen, every caller of one step passes the same row.
 // shp: the shape rows [nprim][8] = {top_offset[3], corner2[3], radius, length} of THIS rollout in THIS step (a row of the table FwdArgs::pshp
@@ -235,7 +236,7 @@ __device__ __attribute__((noinline)) int detect_primitive(const DevSystem &S, co
     int p1 = p0;
     while (p1 < S.nprim && S.prims[p1].group == S.prims[p0].group) p1++;
     f3 w = mk(0, 0, 0);
-    if (wv) { const int g = S.prims[p0].group; w = mk(wg[3 * g], wg[3 * g + 1], wg[3 * g + 2]); }
+    if (wv) { const int g = S.prims[p0].group; w = mk(wg[kPvRow * g], wg[kPvRow * g + 1], wg[kPvRow * g + 2]); }
     const f3 vr = wv ? vel - w : vel;
     for (int k = 0; k < 3; k++) {
       f3 q = pos + vr * (S.h * 0.5f * (float) k);
@@ -271,13 +272,18 @@ __device__ __forceinline__ f3 prim_vout(const DevPrim &p, f3 n) {
   return p.rotates ? cross(mk(0, 1, 0), n) * 8.0f : mk(0, 0, 0);   // Primitive.cpp:254-257, static primitives
 }
 // d of the friction law for a vertex in contact with primitive p: the relative momentum f - m v_out, v_out = v_rot + w (Primitive.cpp's
-// `v_out = this->velocity` plus the rotating sphere's spin). wv: this rollout's [ngroups][3] velocities of the step (dc_set_primitive_velocities),
-// null while none was ever set: then today's expression alone. Evaluated as (f - v_rot m) - w m, so that w = +0 changes no bit.
+// `v_out = this->velocity` plus the rotating sphere's spin). wv: this rollout's [ngroups][kPvRow] motion rows {w, omega} of the step
+// (dc_set_primitive_velocities, dc_set_primitive_spins), null while neither was ever set: then today's expression alone. Evaluated as
+// (f - v_rot m) - w m, so that w = +0 changes no bit. A DC_PRIM_SPHERE of a group whose stored omega is not all +-0 (a test that is uniform per
+// group) adds the surface velocity of its spin, v_spin = radius (omega x n) with the BUILT radius: d = ((f - v_rot m) - w m) - v_spin m. Every
+// other kind has no spin term (its surface velocity would need the contact point, not only the normal).
 __device__ __forceinline__ f3 prim_d(const DevPrim &p, f3 n, f3 f, float m, const float *wv) {
   f3 d = f - prim_vout(p, n) * m;
   if (wv) {
-    const float DC_G *w = (const float DC_G *) wv + 3 * p.group;
+    const float DC_G *w = (const float DC_G *) wv + kPvRow * p.group;
     d = d - mk(w[0], w[1], w[2]) * m;
+    const f3 om = mk(w[3], w[4], w[5]);
+    if (p.kind == DC_PRIM_SPHERE && (om.x != 0.f || om.y != 0.f || om.z != 0.f)) d = d - (cross(om, n) * p.radius) * m;
   }
   return d;
 }

@@ -70,7 +70,8 @@ float *dxf_slot(const dc_ctx *c, int slot) { return c->DXF + xf_elems(c) * slot;
 float *dpar_slot(const dc_ctx *c, int slot) { return c->DPAR + (size_t) c->B * 8 * slot; }
 size_t pc_elems(const dc_ctx *c) { return (size_t) c->B * c->S.nprim * 3; }
 float *pc_slot(const dc_ctx *c, int slot) { return c->PC + pc_elems(c) * slot; }
-size_t pv_elems(const dc_ctx *c) { return (size_t) c->B * c->ngroups * 3; }
+size_t pv_rows(const dc_ctx *c) { return (size_t) c->B * c->ngroups; }      // motion rows {w[3], omega[3]} per slot
+size_t pv_elems(const dc_ctx *c) { return pv_rows(c) * kPvRow; }
 float *pv_slot(const dc_ctx *c, int slot) { return c->PV + pv_elems(c) * slot; }
 float *dpv_slot(const dc_ctx *c, int slot) { return c->DPV + pv_elems(c) * slot; }
 size_t ps_elems(const dc_ctx *c) { return (size_t) c->B * c->S.nprim * kShapeRow; }
@@ -532,13 +533,13 @@ int enqueue_forward_steps(dc_ctx *c, int slot, int nsteps, bool carry_targets, i
   int rc;
   FwdArgs FA = fwd_args(c, slot);          // fused: points x_fixed / fu / fv_scale at the first step's schedule entries
   if (fused) {      // a schedule (dc_set_*_schedule) has to cover all steps of a fused sweep or none of them
-    int nxf = 0, nfu = 0, nfvs = 0, npc = 0, npv = 0, nps = 0;
+    int nxf = 0, nfu = 0, nfvs = 0, npc = 0, npv = 0, nps = 0, npw = 0;
     for (int k = 1; k <= nsteps; k++) {
       nxf += c->sched_xf[slot + k]; nfu += c->sched_fu[slot + k]; nfvs += c->sched_fvs[slot + k]; npc += c->sched_pc[slot + k]; npv += c->sched_pv[slot + k];
-      nps += c->sched_ps[slot + k];
+      nps += c->sched_ps[slot + k]; npw += c->sched_pw[slot + k];
     }
-    if ((nxf % nsteps) || (nfu % nsteps) || (nfvs % nsteps) || (npc % nsteps) || (npv % nsteps) || (nps % nsteps))
-      return fail(c, DC_ERR_INVALID, "dc_rollout_forward: a fixed-point / force / primitive-offset / primitive-velocity / primitive-shape schedule covers only part of the steps " + std::to_string(slot) + " .. " + std::to_string(slot + nsteps));
+    if ((nxf % nsteps) || (nfu % nsteps) || (nfvs % nsteps) || (npc % nsteps) || (npv % nsteps) || (nps % nsteps) || (npw % nsteps))
+      return fail(c, DC_ERR_INVALID, "dc_rollout_forward: a fixed-point / force / primitive-offset / primitive-velocity / primitive-shape / primitive-spin schedule covers only part of the steps " + std::to_string(slot) + " .. " + std::to_string(slot + nsteps));
     if (nxf) FA.slot_xfix = xf_elems(c);
     if (nfu) FA.slot_fu = (size_t) c->B * 3;
     if (nfvs && FA.fv_scale) FA.slot_fvs = (size_t) c->B;
@@ -551,8 +552,15 @@ int enqueue_forward_steps(dc_ctx *c, int slot, int nsteps, bool carry_targets, i
       HIPCHK(c, hipMemcpyAsync(pc_slot(c, slot + k + 1), c->pc_cur, sizeof(float) * pc_elems(c), hipMemcpyDeviceToDevice, c->stream));
       c->pc_row_gen[slot + k + 1] = c->pc_gen;
     }
-    // likewise the obstacle velocities, once a context has them: the row of an unscheduled step takes the current set
-    if (c->PV && !c->sched_pv[slot + k + 1]) HIPCHK(c, hipMemcpyAsync(pv_slot(c, slot + k + 1), c->pv_cur, sizeof(float) * pv_elems(c), hipMemcpyDeviceToDevice, c->stream));
+    // likewise the obstacle motion, once a context has it: the row of an unscheduled step takes the current set, each half (velocity, spin)
+    // where that half has no schedule entry
+    if (c->PV) {
+      const bool sv = c->sched_pv[slot + k + 1], sw = c->sched_pw[slot + k + 1];
+      if (!sv && !sw) HIPCHK(c, hipMemcpyAsync(pv_slot(c, slot + k + 1), c->pv_cur, sizeof(float) * pv_elems(c), hipMemcpyDeviceToDevice, c->stream));
+      else if (!sv || !sw)
+        HIPCHK(c, hipMemcpy2DAsync(pv_slot(c, slot + k + 1) + (sv ? 3 : 0), sizeof(float) * kPvRow, c->pv_cur + (sv ? 3 : 0), sizeof(float) * kPvRow,
+                                   sizeof(float) * 3, pv_rows(c), hipMemcpyDeviceToDevice, c->stream));
+    }
     // and the obstacle shapes: like the centres, a row is copied only when the current set changed since it was written
     if (c->PS && !c->sched_ps[slot + k + 1] && c->ps_row_gen[slot + k + 1] != c->ps_gen) {
       HIPCHK(c, hipMemcpyAsync(ps_slot(c, slot + k + 1), c->ps_cur, sizeof(float) * ps_elems(c), hipMemcpyDeviceToDevice, c->stream));
@@ -1069,7 +1077,7 @@ int dc_alloc_batch(dc_ctx *c, int B, int tape) {
     c->pc_row_gen.assign(slots + 1, 0); c->sched_pc.assign(slots + 1, 0);
     c->pc_gen = 0; c->pc_gen_last = 0;
   }
-  c->PV = c->pv_cur = c->DPV = nullptr; c->sched_pv.assign(slots + 1, 0);      // obstacle velocities: allocated by their first setter
+  c->PV = c->pv_cur = c->DPV = nullptr; c->pv_set = c->pw_set = false; c->sched_pv.assign(slots + 1, 0); c->sched_pw.assign(slots + 1, 0);      // obstacle velocities and spins: allocated by their first setter
   c->PS = c->ps_cur = nullptr; c->sched_ps.assign(slots + 1, 0);      // obstacle shapes: likewise
   c->ps_row_gen.assign(slots + 1, 0); c->ps_gen = 0; c->ps_gen_last = 0;
   {   // ... but the built rows of the batch go up now, while this call synchronises anyway: the first shape setter, which may be a _dev form
@@ -1570,7 +1578,7 @@ int dc_clear_schedules(dc_ctx *c) {
   std::fill(c->sched_xf.begin(), c->sched_xf.end(), 0); std::fill(c->sched_fu.begin(), c->sched_fu.end(), 0);
   std::fill(c->sched_fvs.begin(), c->sched_fvs.end(), 0); std::fill(c->sched_seed.begin(), c->sched_seed.end(), 0);
   std::fill(c->sched_pc.begin(), c->sched_pc.end(), 0);      // (the rows keep their entries until a step overwrites them: pc_row_gen = -1)
-  std::fill(c->sched_pv.begin(), c->sched_pv.end(), 0);
+  std::fill(c->sched_pv.begin(), c->sched_pv.end(), 0); std::fill(c->sched_pw.begin(), c->sched_pw.end(), 0);
   std::fill(c->sched_ps.begin(), c->sched_ps.end(), 0);      // (like the centres: the rows keep their entries until a step overwrites them, ps_row_gen = -1)
   return DC_OK;
 }
@@ -1656,8 +1664,9 @@ int dc_get_primitive_centers(dc_ctx *c, int slot, double *out) {
 // ---- moving obstacles: a velocity w[b][g] per rollout and primitive group, per step (include/diffcloth_hip.h holds the rule). The reference
 //      carries the quantity (v_out = this->velocity in every isInContact of Primitive.cpp) and never sets it ----
 namespace {
-// The velocity table, its current set and the gradient table come with the first setter after dc_alloc_batch, all zero: a context that never
-// calls one hands null pointers to its kernels.
+// The motion table (rows {w[3], omega[3]} per group), its current set and the gradient table come with the first velocity or spin setter after
+// dc_alloc_batch, all zero: a context that never calls one hands null pointers to its kernels. Every entry below addresses its half of the
+// rows (half 0 = w, 1 = omega); the caller's layout is the dense [..][B][G][3] of either kind.
 int ensure_velocities(dc_ctx *c) {
   if (c->PV) return DC_OK;
   const size_t per = pv_elems(c), slots = (size_t) c->tape + 1;
@@ -1672,94 +1681,156 @@ int ensure_velocities(dc_ctx *c) {
   c->PV = pv; c->pv_cur = cur; c->DPV = dpv;      // (steps enqueued from here on see the table; those already enqueued ran the static law)
   return DC_OK;
 }
-// host values -> fp32 in `dst` (n floats); null = zeros. Synchronises, like the host forms of the offsets.
-int upload_velocities(dc_ctx *c, const double *w, float *dst, size_t n) {
-  std::vector<float> v(n, 0.0f);
-  if (w) for (size_t k = 0; k < n; k++) v[k] = (float) w[k];
+// host values [rows][3] -> fp32 in one half of `rows` motion rows at `dst`; null = zeros. Synchronises, like the host forms of the offsets.
+int upload_motion(dc_ctx *c, const double *w, float *dst, size_t rows, int half) {
+  std::vector<float> v(rows * 3, 0.0f);
+  if (w) for (size_t k = 0; k < v.size(); k++) v[k] = (float) w[k];
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(dst, v.data(), n * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy2D(dst + 3 * half, sizeof(float) * kPvRow, v.data(), sizeof(float) * 3, sizeof(float) * 3, rows, hipMemcpyHostToDevice));
+  return DC_OK;
+}
+// one half of `rows` motion rows at `src` -> host [rows][3], widened. Synchronises.
+int download_motion(dc_ctx *c, const float *src, double *out, size_t rows, int half) {
+  std::vector<float> v(rows * 3);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy2D(v.data(), sizeof(float) * 3, src + 3 * half, sizeof(float) * kPvRow, sizeof(float) * 3, rows, hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < v.size(); k++) out[k] = v[k];
+  return DC_OK;
+}
+// What a host spin setter refuses: a value that is not finite, and a non-zero omega for a group that holds no DC_PRIM_SPHERE (the term would be
+// silently zero there). omega: [rows][G][3].
+int check_spins(dc_ctx *c, const char *who, const double *omega, size_t rows) {
+  if (!omega) return DC_OK;
+  const int G = c->ngroups;
+  std::vector<char> has_sphere(G, 0);
+  for (size_t k = 0; k < c->prims.size(); k++) if (c->prims[k].kind == DC_PRIM_SPHERE) has_sphere[c->group_of_prim[k]] = 1;
+  for (size_t r = 0; r < rows; r++)
+    for (int g = 0; g < G; g++)
+      for (int q = 0; q < 3; q++) {
+        const double v = omega[(r * G + g) * 3 + q];
+        if (!std::isfinite(v)) return fail(c, DC_ERR_INVALID, std::string(who) + ": an angular velocity is not finite");
+        if (v != 0.0 && !has_sphere[g])
+          return fail(c, DC_ERR_INVALID, std::string(who) + ": primitive group " + std::to_string(g) + " holds no DC_PRIM_SPHERE; only a sphere has a spin term");
+      }
+  return DC_OK;
+}
+void mark_motion_set(dc_ctx *c, int half) { (half ? c->pw_set : c->pv_set) = true; }
+bool motion_was_set(const dc_ctx *c, int half) { return half ? c->pw_set : c->pv_set; }
+void mark_motion_scheduled(dc_ctx *c, int half, int slot0, int nsteps) {
+  std::vector<char> &s = half ? c->sched_pw : c->sched_pv;
+  for (int k = 1; k <= nsteps; k++) s[slot0 + k] = 1;
+}
+
+// the bodies of the velocity (half 0) and spin (half 1) entries
+int set_motion(dc_ctx *c, const char *who, int half, const double *w) {
+  int rc = check_offsets(c, who, 0, 0);
+  if (rc) return rc;
+  if (half && (rc = check_spins(c, who, w, (size_t) c->B))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = ensure_velocities(c))) return rc;
+  mark_motion_set(c, half);
+  return upload_motion(c, w, c->pv_cur, pv_rows(c), half);
+}
+int set_motion_dev(dc_ctx *c, const char *who, int half, const void *d_w, int is_f32) {
+  int rc = check_offsets(c, who, 0, 0);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = ensure_velocities(c))) return rc;
+  mark_motion_set(c, half);
+  if (d_w) launch_cast_in_half(d_w, is_f32, c->pv_cur, (long) pv_rows(c), half, c->stream);
+  else HIPCHK(c, hipMemset2DAsync(c->pv_cur + 3 * half, sizeof(float) * kPvRow, 0, sizeof(float) * 3, pv_rows(c), c->stream));
+  HIPCHK(c, hipGetLastError());
+  return DC_OK;
+}
+int set_motion_schedule(dc_ctx *c, const char *who, int half, int slot0, int nsteps, const double *w) {
+  int rc = check_offsets(c, who, slot0, slot0 + nsteps);
+  if (rc) return rc;
+  if (nsteps < 1 || !w) return fail(c, DC_ERR_INVALID, std::string(who) + ": null schedule");
+  if (half && (rc = check_spins(c, who, w, (size_t) nsteps * c->B))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = ensure_velocities(c))) return rc;
+  mark_motion_set(c, half);
+  if ((rc = upload_motion(c, w, pv_slot(c, slot0 + 1), pv_rows(c) * nsteps, half))) return rc;
+  mark_motion_scheduled(c, half, slot0, nsteps);
+  return DC_OK;
+}
+int set_motion_schedule_dev(dc_ctx *c, const char *who, int half, int slot0, int nsteps, const void *d_w, int is_f32) {
+  int rc = check_offsets(c, who, slot0, slot0 + nsteps);
+  if (rc) return rc;
+  if (nsteps < 1 || !d_w) return fail(c, DC_ERR_INVALID, std::string(who) + ": null schedule");
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = ensure_velocities(c))) return rc;
+  mark_motion_set(c, half);
+  launch_cast_in_half(d_w, is_f32, pv_slot(c, slot0 + 1), (long) (pv_rows(c) * nsteps), half, c->stream);      // one launch for all slots
+  HIPCHK(c, hipGetLastError());
+  mark_motion_scheduled(c, half, slot0, nsteps);
+  return DC_OK;
+}
+int get_motion(dc_ctx *c, const char *who, int half, int slot, double *w) {
+  int rc = check_batch(c, slot, slot);
+  if (rc) return rc;
+  if (slot < 1 || !w) return fail(c, DC_ERR_INVALID, std::string(who) + ": slot 0 has no record");
+  const size_t n = pv_rows(c) * 3;
+  if (!c->PV || !n) {      // (none was ever set: the step used none)
+    for (size_t k = 0; k < n; k++) w[k] = 0.0;
+    return DC_OK;
+  }
+  return download_motion(c, pv_slot(c, slot), w, pv_rows(c), half);
+}
+int get_motion_gradients(dc_ctx *c, const char *who, int half, int slot0, int nslots, double *out) {
+  int rc = check_batch(c, slot0, slot0 + nslots - 1);
+  if (rc) return rc;
+  if (slot0 < 1 || nslots < 1 || !out) return fail(c, DC_ERR_INVALID, std::string(who) + ": slot 0 has no record");
+  if (!c->PV || !motion_was_set(c, half))
+    return fail(c, DC_ERR_STATE, std::string(who) + (half ? ": no primitive spin has been set on this batch" : ": no primitive velocity has been set on this batch"));
+  return download_motion(c, dpv_slot(c, slot0), out, pv_rows(c) * nslots, half);
+}
+int get_motion_gradients_dev(dc_ctx *c, const char *who, int half, int slot0, int nslots, void *d_out, int is_f32) {
+  int rc = check_batch(c, slot0, slot0 + nslots - 1);
+  if (rc) return rc;
+  if (slot0 < 1 || nslots < 1 || !d_out) return fail(c, DC_ERR_INVALID, std::string(who) + ": slot 0 has no record");
+  if (!c->PV || !motion_was_set(c, half))
+    return fail(c, DC_ERR_STATE, std::string(who) + (half ? ": no primitive spin has been set on this batch" : ": no primitive velocity has been set on this batch"));
+  HIPCHK(c, hipSetDevice(c->device));
+  launch_copy_cast_half(dpv_slot(c, slot0), d_out, is_f32, (long) (pv_rows(c) * nslots), half, c->stream);
+  HIPCHK(c, hipGetLastError());
   return DC_OK;
 }
 }  // namespace
 
-int dc_set_primitive_velocities(dc_ctx *c, const double *w) {
-  int rc = check_offsets(c, "dc_set_primitive_velocities", 0, 0);
-  if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = ensure_velocities(c))) return rc;
-  return upload_velocities(c, w, c->pv_cur, pv_elems(c));
-}
-
-int dc_set_primitive_velocities_dev(dc_ctx *c, const void *d_w, int is_f32) {
-  int rc = check_offsets(c, "dc_set_primitive_velocities_dev", 0, 0);
-  if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = ensure_velocities(c))) return rc;
-  if (d_w) launch_cast_in(d_w, is_f32, c->pv_cur, (long) pv_elems(c), c->stream);
-  else HIPCHK(c, hipMemsetAsync(c->pv_cur, 0, sizeof(float) * pv_elems(c), c->stream));
-  HIPCHK(c, hipGetLastError());
-  return DC_OK;
-}
-
+int dc_set_primitive_velocities(dc_ctx *c, const double *w) { return set_motion(c, "dc_set_primitive_velocities", 0, w); }
+int dc_set_primitive_velocities_dev(dc_ctx *c, const void *d_w, int is_f32) { return set_motion_dev(c, "dc_set_primitive_velocities_dev", 0, d_w, is_f32); }
 int dc_set_primitive_velocity_schedule(dc_ctx *c, int slot0, int nsteps, const double *w) {
-  int rc = check_offsets(c, "dc_set_primitive_velocity_schedule", slot0, slot0 + nsteps);
-  if (rc) return rc;
-  if (nsteps < 1 || !w) return fail(c, DC_ERR_INVALID, "dc_set_primitive_velocity_schedule: null schedule");
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = ensure_velocities(c))) return rc;
-  if ((rc = upload_velocities(c, w, pv_slot(c, slot0 + 1), pv_elems(c) * nsteps))) return rc;
-  for (int k = 1; k <= nsteps; k++) c->sched_pv[slot0 + k] = 1;
-  return DC_OK;
+  return set_motion_schedule(c, "dc_set_primitive_velocity_schedule", 0, slot0, nsteps, w);
 }
-
 int dc_set_primitive_velocity_schedule_dev(dc_ctx *c, int slot0, int nsteps, const void *d_w, int is_f32) {
-  int rc = check_offsets(c, "dc_set_primitive_velocity_schedule_dev", slot0, slot0 + nsteps);
-  if (rc) return rc;
-  if (nsteps < 1 || !d_w) return fail(c, DC_ERR_INVALID, "dc_set_primitive_velocity_schedule_dev: null schedule");
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = ensure_velocities(c))) return rc;
-  launch_cast_in(d_w, is_f32, pv_slot(c, slot0 + 1), (long) (pv_elems(c) * nsteps), c->stream);      // one launch for all slots
-  HIPCHK(c, hipGetLastError());
-  for (int k = 1; k <= nsteps; k++) c->sched_pv[slot0 + k] = 1;
-  return DC_OK;
+  return set_motion_schedule_dev(c, "dc_set_primitive_velocity_schedule_dev", 0, slot0, nsteps, d_w, is_f32);
 }
-
-int dc_get_primitive_velocities(dc_ctx *c, int slot, double *w) {
-  int rc = check_batch(c, slot, slot);
-  if (rc) return rc;
-  if (slot < 1 || !w) return fail(c, DC_ERR_INVALID, "dc_get_primitive_velocities: slot 0 has no record");
-  std::vector<float> v(pv_elems(c), 0.0f);      // (no velocity was ever set: the step used none)
-  if (c->PV && !v.empty()) {
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(v.data(), pv_slot(c, slot), v.size() * sizeof(float), hipMemcpyDeviceToHost));
-  }
-  for (size_t k = 0; k < v.size(); k++) w[k] = v[k];
-  return DC_OK;
-}
-
+int dc_get_primitive_velocities(dc_ctx *c, int slot, double *w) { return get_motion(c, "dc_get_primitive_velocities", 0, slot, w); }
 int dc_get_primitive_velocity_gradients(dc_ctx *c, int slot0, int nslots, double *dL_dw) {
-  int rc = check_batch(c, slot0, slot0 + nslots - 1);
-  if (rc) return rc;
-  if (slot0 < 1 || nslots < 1 || !dL_dw) return fail(c, DC_ERR_INVALID, "dc_get_primitive_velocity_gradients: slot 0 has no record");
-  if (!c->PV) return fail(c, DC_ERR_STATE, "dc_get_primitive_velocity_gradients: no primitive velocity has been set on this batch");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::vector<float> v(pv_elems(c) * nslots);
-  HIPCHK(c, hipMemcpy(v.data(), dpv_slot(c, slot0), v.size() * sizeof(float), hipMemcpyDeviceToHost));
-  for (size_t k = 0; k < v.size(); k++) dL_dw[k] = v[k];
-  return DC_OK;
+  return get_motion_gradients(c, "dc_get_primitive_velocity_gradients", 0, slot0, nslots, dL_dw);
+}
+int dc_get_primitive_velocity_gradients_dev(dc_ctx *c, int slot0, int nslots, void *d_dL_dw, int is_f32) {
+  return get_motion_gradients_dev(c, "dc_get_primitive_velocity_gradients_dev", 0, slot0, nslots, d_dL_dw, is_f32);
 }
 
-int dc_get_primitive_velocity_gradients_dev(dc_ctx *c, int slot0, int nslots, void *d_dL_dw, int is_f32) {
-  int rc = check_batch(c, slot0, slot0 + nslots - 1);
-  if (rc) return rc;
-  if (slot0 < 1 || nslots < 1 || !d_dL_dw) return fail(c, DC_ERR_INVALID, "dc_get_primitive_velocity_gradients_dev: slot 0 has no record");
-  if (!c->PV) return fail(c, DC_ERR_STATE, "dc_get_primitive_velocity_gradients_dev: no primitive velocity has been set on this batch");
-  HIPCHK(c, hipSetDevice(c->device));
-  launch_copy_cast(dpv_slot(c, slot0), d_dL_dw, is_f32, (long) (pv_elems(c) * nslots), c->stream);
-  HIPCHK(c, hipGetLastError());
-  return DC_OK;
+// ---- spinning obstacles: an angular velocity omega[b][g] per rollout and primitive group, per step: the other half of the motion rows, under
+//      the rules of the velocity entries (include/diffcloth_hip.h holds the rule). The reference's only spin is its hard-wired `rotates` sphere ----
+int dc_set_primitive_spins(dc_ctx *c, const double *omega) { return set_motion(c, "dc_set_primitive_spins", 1, omega); }
+int dc_set_primitive_spins_dev(dc_ctx *c, const void *d_omega, int is_f32) { return set_motion_dev(c, "dc_set_primitive_spins_dev", 1, d_omega, is_f32); }
+int dc_set_primitive_spin_schedule(dc_ctx *c, int slot0, int nsteps, const double *omega) {
+  return set_motion_schedule(c, "dc_set_primitive_spin_schedule", 1, slot0, nsteps, omega);
+}
+int dc_set_primitive_spin_schedule_dev(dc_ctx *c, int slot0, int nsteps, const void *d_omega, int is_f32) {
+  return set_motion_schedule_dev(c, "dc_set_primitive_spin_schedule_dev", 1, slot0, nsteps, d_omega, is_f32);
+}
+int dc_get_primitive_spins(dc_ctx *c, int slot, double *omega) { return get_motion(c, "dc_get_primitive_spins", 1, slot, omega); }
+int dc_get_primitive_spin_gradients(dc_ctx *c, int slot0, int nslots, double *dL_domega) {
+  return get_motion_gradients(c, "dc_get_primitive_spin_gradients", 1, slot0, nslots, dL_domega);
+}
+int dc_get_primitive_spin_gradients_dev(dc_ctx *c, int slot0, int nslots, void *d_dL_domega, int is_f32) {
+  return get_motion_gradients_dev(c, "dc_get_primitive_spin_gradients_dev", 1, slot0, nslots, d_dL_domega, is_f32);
 }
 
 // ---- obstacle shapes: a row {top_offset[3], corner2[3], radius, length} per rollout, flattened primitive and step (dc_primshape.h holds the

@@ -36,7 +36,7 @@ __global__ __launch_bounds__(THREADS) void k_pd_step(const DevSystem *__restrict
   int *rec_prim = A.rec_prim + (size_t) b * N;
   const float *xfix = A.x_fixed + (size_t) b * 3 * S.Af;
   const float *mu = A.mu + (size_t) b * S.ngroups;
-  const float *pvel_b = A.pvel ? A.pvel + (size_t) b * 3 * S.ngroups : nullptr;      // this step's obstacle velocities of this rollout (null: none set)
+  const float *pvel_b = A.pvel ? A.pvel + (size_t) b * kPvRow * S.ngroups : nullptr;      // this step's obstacle velocities of this rollout (null: none set)
   const float *pshp_b = A.pshp ? A.pshp + (size_t) b * 8 * S.nprim : nullptr;        // this step's obstacle shapes of this rollout (null: DevPrim's)
   const float h = S.h;
   const f3 grav = mk(S.gx, S.gy, S.gz);

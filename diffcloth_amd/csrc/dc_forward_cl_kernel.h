@@ -155,7 +155,7 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_cl(const DevSystem *__restr
   const float *fu_s = A.fu ? A.fu + (size_t) step * A.slot_fu : nullptr;
   const float *fvs_s = A.fv_scale ? A.fv_scale + (size_t) step * A.slot_fvs : nullptr;
   const float *pcen_s = A.pcen + (size_t) step * A.slot_pcen;      // this step's primitive centres, all rollouts
-  const float *pvel_s = A.pvel ? A.pvel + (size_t) step * A.slot_pvel + (size_t) b * 3 * S.ngroups : nullptr;      // this step's obstacle velocities of this rollout (null: none set)
+  const float *pvel_s = A.pvel ? A.pvel + (size_t) step * A.slot_pvel + (size_t) b * kPvRow * S.ngroups : nullptr;      // this step's obstacle velocities of this rollout (null: none set)
   const float *pvel_all = A.pvel ? A.pvel + (size_t) step * A.slot_pvel : nullptr;
   const float *pshp_all = A.pshp ? A.pshp + (size_t) step * A.slot_pshp : nullptr;      // this step's obstacle shapes, all rollouts (null: DevPrim's)
   const float *pshp_s = pshp_all ? pshp_all + (size_t) b * 8 * S.nprim : nullptr;

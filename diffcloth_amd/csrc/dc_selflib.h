@@ -188,7 +188,7 @@ __device__ __forceinline__ void self_detect_rollout(const DevSystem &S, const De
     // primitive contacts seed the layering frontier (Simulation.cpp:455-460); the step kernel recomputes the same
     // flags (same inputs — the same row of primitive centres among them —, same code) and also stores the normals
     f3 nrm;
-    rec_prim_all[(size_t) b * N + i] = detect_primitive(S, pcen_all + (size_t) b * 3 * S.nprim, pvel_all ? pvel_all + (size_t) b * 3 * S.ngroups : nullptr,
+    rec_prim_all[(size_t) b * N + i] = detect_primitive(S, pcen_all + (size_t) b * 3 * S.nprim, pvel_all ? pvel_all + (size_t) b * kPvRow * S.ngroups : nullptr,
                                                         pshp_all ? pshp_all + (size_t) b * 8 * S.nprim : nullptr, x, v, nrm);
   }
   float maxd[3], mind[3];

@@ -172,7 +172,7 @@ _ROLLOUT_INPUTS = ("x0", "v0", "actions", "uniform_force", "vertex_force_scale",
 
 
 def _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets=None, primitive_velocities=None,
-                   primitive_shapes=None):
+                   primitive_shapes=None, primitive_spins=None):
     """Checks the arguments of sim_rollout against the engine's sizes and returns the episode length T. Touches no device."""
     e = sim.engine
     B, N, Af, G = e.B, e.N, e.Af, e.ngroups
@@ -180,6 +180,7 @@ def _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scal
     given["primitive_offsets"] = primitive_offsets
     given["primitive_velocities"] = primitive_velocities
     given["primitive_shapes"] = primitive_shapes
+    given["primitive_spins"] = primitive_spins
     if torch.is_tensor(primitive_offsets) and primitive_offsets.requires_grad:
         raise ValueError("sim_rollout: primitive_offsets requires grad, but there is no gradient with respect to an obstacle's centre: the adjoint "
                          "holds the contact normals of the record constant, as the reference's does. Pass primitive_offsets.detach()")
@@ -216,6 +217,8 @@ def _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scal
             T = int(given[name].shape[0])
     if T is None and primitive_shapes is not None and primitive_shapes.dim() == 4:
         T = int(primitive_shapes.shape[0])
+    if T is None and primitive_spins is not None and primitive_spins.dim() == 4:
+        T = int(primitive_spins.shape[0])
     if T is None:
         if steps is None:
             raise ValueError("sim_rollout: no schedule given, pass steps=")
@@ -227,7 +230,7 @@ def _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scal
     want = dict(x0=(B, 3 * N), v0=(B, 3 * N), actions=(T, B, 3 * Af), uniform_force=(T, B, 3), vertex_force_scale=(T, B),
                 vertex_forces=(B, 3 * N), mu=(B, G))
     for name, t in given.items():
-        if name in ("primitive_offsets", "primitive_velocities"):
+        if name in ("primitive_offsets", "primitive_velocities", "primitive_spins"):
             if t is not None and tuple(t.shape) not in ((T, B, G, 3), (B, G, 3)):
                 raise ValueError(f"sim_rollout: wrong shape: {name} is {tuple(t.shape)}, expected {(T, B, G, 3)} (one per step) or {(B, G, 3)}")
         elif name == "primitive_shapes":
@@ -249,7 +252,7 @@ def _np64(t):
 class RolloutFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, sim, T, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets=None, primitive_velocities=None,
-                primitive_shapes=None):
+                primitive_shapes=None, primitive_spins=None):
         e = sim.engine
         B, N = e.B, e.N
         if primitive_offsets is not None and primitive_offsets.dim() == 3:      # constant over the episode: the same entry in every step
@@ -259,6 +262,9 @@ class RolloutFunction(torch.autograd.Function):
             primitive_velocities = primitive_velocities.detach().unsqueeze(0).expand(T, *primitive_velocities.shape)
         if primitive_shapes is not None and primitive_shapes.dim() == 3:
             primitive_shapes = primitive_shapes.detach().unsqueeze(0).expand(T, *primitive_shapes.shape)
+        ctx.spins_per_episode = primitive_spins is not None and primitive_spins.dim() == 3      # (its gradient: summed over the steps)
+        if ctx.spins_per_episode:
+            primitive_spins = primitive_spins.detach().unsqueeze(0).expand(T, *primitive_spins.shape)
         sim._episode += 1
         ctx.sim, ctx.T, ctx.episode = sim, T, sim._episode
         ctx.save_for_backward(vertex_forces, vertex_force_scale)
@@ -283,6 +289,8 @@ class RolloutFunction(torch.autograd.Function):
                 e.set_primitive_velocity_schedule_dev(0, T, primitive_velocities.detach())
             if primitive_shapes is not None:
                 e.set_primitive_shape_schedule_dev(0, T, primitive_shapes.detach())
+            if primitive_spins is not None:
+                e.set_primitive_spin_schedule_dev(0, T, primitive_spins.detach())
             e.rollout_forward_async(0, T)
             xs = torch.empty((T, B, 3 * N), dtype=x0.dtype, device=x0.device)
             vs = torch.empty_like(xs)
@@ -306,6 +314,8 @@ class RolloutFunction(torch.autograd.Function):
             e.set_primitive_velocity_schedule(0, _np64(primitive_velocities))
         if primitive_shapes is not None:
             e.set_primitive_shape_schedule(0, _np64(primitive_shapes))
+        if primitive_spins is not None:
+            e.set_primitive_spin_schedule(0, _np64(primitive_spins))
         e.rollout_forward(0, T)
         xs, vs = e.get_states(1, T)
         sim.step_idx = T
@@ -321,6 +331,7 @@ class RolloutFunction(torch.autograd.Function):
         vertex_forces, vertex_force_scale = ctx.saved_tensors
         _, _, _, _, need_a, need_fu, need_fvs, need_fv, need_mu = ctx.needs_input_grad[:9]
         need_w = len(ctx.needs_input_grad) > 10 and ctx.needs_input_grad[10]
+        need_om = len(ctx.needs_input_grad) > 12 and ctx.needs_input_grad[12]
         keep = bool(need_fvs or need_fv)
         sim._bwd_slots.update(range(1, T + 1))
         dt = grad_xs.dtype
@@ -353,8 +364,14 @@ class RolloutFunction(torch.autograd.Function):
                 e.get_primitive_velocity_gradients_dev(1, T, dw)
                 if ctx.velocities_per_episode:
                     dw = dw.sum(0)
+            dom = None
+            if need_om:
+                dom = new(T, B, G, 3)
+                e.get_primitive_spin_gradients_dev(1, T, dom)
+                if ctx.spins_per_episode:
+                    dom = dom.sum(0)
             sim.check_episode()                # the single synchronisation of the episode: errors of both sweeps surface here
-            return None, None, dx0, dv0, da, dfu, dfvs, dfv, dmu, None, dw, None
+            return None, None, dx0, dv0, da, dfu, dfvs, dfv, dmu, None, dw, None, dom
         gxs, gvs = _np64(grad_xs), _np64(grad_vs)
         e.keep_force_gradients(keep)
         zero = np.zeros((1, B, 3 * N))
@@ -377,12 +394,16 @@ class RolloutFunction(torch.autograd.Function):
         if need_w:
             dw = e.get_primitive_velocity_gradients(1, T)
             dw = t(dw.sum(0) if ctx.velocities_per_episode else dw)
+        dom = None
+        if need_om:
+            dom = e.get_primitive_spin_gradients(1, T)
+            dom = t(dom.sum(0) if ctx.spins_per_episode else dom)
         sim.check_episode()
-        return None, None, t(dx0), t(dv0), da, dfu, dfvs, dfv, (t(dmu) if need_mu else None), None, dw, None
+        return None, None, t(dx0), t(dv0), da, dfu, dfvs, dfv, (t(dmu) if need_mu else None), None, dw, None, dom
 
 
 def sim_rollout(sim, x0, v0, actions=None, *, steps=None, uniform_force=None, vertex_force_scale=None, vertex_forces=None, mu=None,
-                primitive_offsets=None, primitive_velocities=None, primitive_shapes=None):
+                primitive_offsets=None, primitive_velocities=None, primitive_shapes=None, primitive_spins=None):
     """A whole differentiable episode of all rollouts: the states after every step, (xs, vs), [T, B, 3N] each in the dtype of x0.
 
     x0, v0: [B, 3N] initial state. actions: [T, B, 3 Af] clip targets of every step. uniform_force: [T, B, 3] force on every vertex per
@@ -410,6 +431,13 @@ def sim_rollout(sim, x0, v0, actions=None, *, steps=None, uniform_force=None, ve
     default) apply. A tensor that requires grad is refused: the adjoint does not see an obstacle's shape. A shape schedule alone leaves
     the surface static in the friction law; the translation part of a swinging obstacle's motion goes into primitive_velocities.
 
+    primitive_spins: [T, B, G, 3] angular velocity (rad/s) of every primitive group per step and rollout, or [B, G, 3] for the whole
+    episode (Engine.set_primitive_spin_schedule: a DC_PRIM_SPHERE of the group adds the surface velocity radius (omega x n) to the
+    obstacle's velocity in the friction law, with its built radius; every other kind has no spin term, and a non-zero value for a group
+    without a sphere is refused on the host path). When omitted the schedule is cleared like the others and the engine's current spins
+    (Engine.set_primitive_spins; none by default) apply. A tensor that requires grad receives dL/domega of every step, summed over the
+    steps for the [B, G, 3] form (normals and contact set held constant, as everywhere in the adjoint).
+
     The episode occupies tape slots 0 .. T (T <= the tape of alloc_batch) and replaces what the tape held: the function sets the trajectory
     start to slot 0, clears the schedules it does not set, and leaves sim.step_idx = T. `mu` and `vertex_forces`, when given, stay set on
     the engine as after Engine.set_mu / set_vertex_forces; when omitted the engine's current values apply, as does its current uniform
@@ -423,9 +451,9 @@ def sim_rollout(sim, x0, v0, actions=None, *, steps=None, uniform_force=None, ve
     The action gradient is dL_dxfixed of every step as the adjoint gives it: it is NOT rescaled. The clamp of its norm belongs to
     `sim_step`, which mirrors the reference's per-step function (functional.py:88-97)."""
     T = _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets, primitive_velocities,
-                       primitive_shapes)
+                       primitive_shapes, primitive_spins)
     return RolloutFunction.apply(sim, T, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets,
-                                 primitive_velocities, primitive_shapes)
+                                 primitive_velocities, primitive_shapes, primitive_spins)
 
 
 def rotated_primitive_shapes(shapes, R):

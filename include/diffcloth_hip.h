@@ -363,7 +363,8 @@ int dc_get_primitive_centers(dc_ctx *ctx, int slot, double *c /*B*P*3*/);
  *     absolute vel; the two agree wherever the reference is exercised, w = 0.) With both, the step is Galilean invariant: every obstacle moving at
  *     w and the cloth at (x, v + w) — attachment targets moved by w h — is the static step at (x, v), shifted by (w h, w).
  * A caller who moves an obstacle along c(t) passes offsets[s] = c(t_s) - c_built and velocities[s] = (c(t_{s+1}) - c(t_s)) / h.
- * Storage: a table [slot][B][G][3], per GROUP, allocated by the first of these setters after dc_alloc_batch; until then the kernels evaluate the
+ * Storage: a table of rows {w[3], omega[3]} [slot][B][G][6], per GROUP, shared with the spin entries below and allocated (all zero) by the first
+ * setter of either kind after dc_alloc_batch; every entry addresses its half, so the layouts here stay B*G*3. Until then the kernels evaluate the
  * static law (a null pointer: one uniform branch in the forward kernels, and the adjoint step kernels of such a context are the instances compiled
  * without the table). Row `slot` is what the step that PRODUCED `slot` used and what the backward step through record
  * `slot` reads: a record handed in with dc_set_record at `slot` gets its velocity from a one-step schedule at slot - 1.
@@ -388,6 +389,38 @@ int dc_set_primitive_velocity_schedule_dev(dc_ctx *ctx, int slot0, int nsteps, c
 int dc_get_primitive_velocities(dc_ctx *ctx, int slot, double *w /*B*G*3*/);
 int dc_get_primitive_velocity_gradients(dc_ctx *ctx, int slot0, int nslots, double *dL_dw /*nslots*B*G*3*/);
 int dc_get_primitive_velocity_gradients_dev(dc_ctx *ctx, int slot0, int nslots, void *d_dL_dw /*nslots*B*G*3*/, int is_f32);
+/* ---- spinning obstacles: an angular velocity per rollout, primitive group and step. The reference's only spin is its hard-wired `rotates`
+ * sphere (fixed axis, fixed speed, no gradient). ONE rule, next to the centre and velocity rules above: rollout b, group g and step have
+ * omega[b][g][3] in rad/s; the device stores fp32(omega), the fp64 operator of the adjoint uses (double) fp32(omega). It enters the step in ONE
+ * place, the v_out of the friction law: for a vertex in contact with a flattened primitive p of group g whose kind is DC_PRIM_SPHERE
+ *         v_spin = radius_p (omega[b][g] x n)         (radius_p: the BUILT radius; n: the contact normal the law already uses)
+ *         d = ((f - v_rot(p, n) m) - w[b][g] m) - v_spin m
+ * evaluated in this order and skipped, by a test that is uniform per group, when all three components of the stored omega are +-0: omega = 0 and
+ * "never set" are the same step bit for bit, with and without velocities. Every other kind has NO spin term — plane, bowl, capsule, the
+ * discretised sphere (its normal is a face normal) and the capsule child of a LowerLeg; the sphere children of a LowerLeg do contribute (about
+ * their own centres). The reference's rotates sphere is the special case omega = (0, 8 / radius, 0); `rotates` stays as it is and the two add.
+ * Detection is unchanged: a sphere spinning about its centre occupies the same space. The term applies in every forward kernel family, in the
+ * fp32 adjoint operators, in the fp64 operator, the fall-back and dL_dmu (recorded and dc_set_record branches). A caller who also changes the
+ * radius through a shape schedule scales omega by r_step / r_built themselves: the adjoint does not read the shape.
+ * The entries mirror the velocity entries and every rule there holds: row `slot` is what the step that PRODUCED `slot` used and what the backward
+ * step through record `slot` reads (a dc_set_record record gets its spin from a one-step schedule at slot - 1); an entry stays until it is
+ * overwritten, dc_clear_schedules or dc_alloc_batch; the per-step calls honour the schedule; a fused sweep needs it on all of its steps or on
+ * none (DC_ERR_INVALID; spin entries and velocity entries are tracked separately); dc_alloc_batch, dc_set_primitives and dc_build drop
+ * everything; a host-only context answers DC_ERR_STATE; G == 0 gives DC_ERR_INVALID. The host setters refuse (DC_ERR_INVALID) a value
+ * that is not finite and a non-zero omega for a group that holds no DC_PRIM_SPHERE. The _dev forms take DEVICE pointers (fp32 or fp64) on the context's
+ * stream — one launch for all slots, no synchronisation — and cannot look: there the term is simply zero for such a group.
+ * The gradient, under the adjoint's own rules (normals constant, contact set not differentiated), with g_i = (dr_i/dd_i)^T u_i:
+ *         dL/domega[b][g] = -h * sum over the vertices i in contact with a DC_PRIM_SPHERE p of group g of  m_i radius_p (n_i x g_i)
+ * summed in fp64 without atomics (bit-reproducible, one workgroup or split), written per record slot and OVERWRITTEN by the next backward step
+ * through that slot, as dL/dw is. dL_ddensity keeps the reference's omission (adddr_dd = false). The gradient getters fail with DC_ERR_STATE
+ * before any spin setter.                                                                                                                    */
+int dc_set_primitive_spins(dc_ctx *ctx, const double *omega /*B*G*3 or NULL = zeros*/);
+int dc_set_primitive_spin_schedule(dc_ctx *ctx, int slot0, int nsteps, const double *omega /*nsteps*B*G*3*/);
+int dc_set_primitive_spins_dev(dc_ctx *ctx, const void *d_omega /*B*G*3 or NULL = zeros*/, int is_f32);
+int dc_set_primitive_spin_schedule_dev(dc_ctx *ctx, int slot0, int nsteps, const void *d_omega /*nsteps*B*G*3*/, int is_f32);
+int dc_get_primitive_spins(dc_ctx *ctx, int slot, double *omega /*B*G*3*/);
+int dc_get_primitive_spin_gradients(dc_ctx *ctx, int slot0, int nslots, double *dL_domega /*nslots*B*G*3*/);
+int dc_get_primitive_spin_gradients_dev(dc_ctx *ctx, int slot0, int nslots, void *d_dL_domega /*nslots*B*G*3*/, int is_f32);
 /* ---- obstacle shapes per rollout and step: radius, capsule axis and length, the two corners of a finite plane. ONE rule, next to the two above:
  * a SHAPE ROW of 8 numbers per rollout b and FLATTENED primitive p (dc_set_primitives order, P <= 8; per primitive, not per group: the children
  * of a LowerLeg each have their own), the dc_primitive fields of the same names,
@@ -400,7 +433,8 @@ int dc_get_primitive_velocity_gradients_dev(dc_ctx *ctx, int slot0, int nslots, 
  * the centre" test stays world-up. For a DC_PRIM_SPHERE_DISCRETIZED the kernels do NOT read the row — its face table is built for one radius —
  * and the host setters refuse (DC_ERR_INVALID) a row for it that differs from the built one after rounding.
  * A shape schedule alone leaves the surface STATIC in the friction law, as an offset alone does: the surface velocity of a rotating or growing
- * obstacle is not modelled. A caller who wants the translation part passes velocities (dc_set_primitive_velocities). There is no gradient with
+ * obstacle is not modelled. A caller who wants the translation part passes velocities (dc_set_primitive_velocities); the spin of a sphere is
+ * given through the spin entries (dc_set_primitive_spins). There is no gradient with
  * respect to a shape: the adjoint holds the record's normals and contact set constant and does not read the shape at all.
  * Storage: a table [slot][B][P][8] in fp32 and a current set [B][P][8], allocated by the first of these setters after dc_alloc_batch and filled
  * with the built shapes; until then the kernels read the built primitive table (a null pointer: one uniform branch). Row `slot` is what the step
