@@ -58,7 +58,7 @@ EXPORTED_SYMBOLS = [
     "dc_get_vertex_data", "dc_alloc_batch", "dc_set_state", "dc_get_state", "dc_set_mu", "dc_set_uniform_force", "dc_set_vertex_forces", "dc_set_vertex_force_field", "dc_get_force_gradient",
     "dc_step_forward", "dc_get_record", "dc_get_contacts", "dc_get_self_contacts", "dc_step_backward", "dc_rollout_forward",
     "dc_seed_gradient", "dc_rollout_backward", "dc_get_gradient", "dc_get_param_gradients", "dc_get_stats", "dc_sync", "dc_timer_start",
-    "dc_timer_stop", "dc_kernel_times", "dc_get_cluster", "dc_set_gradient", "dc_set_fixed_point_schedule", "dc_set_force_schedule",
+    "dc_timer_stop", "dc_kernel_times", "dc_get_cluster", "dc_get_cluster_rows", "dc_set_gradient", "dc_set_fixed_point_schedule", "dc_set_force_schedule",
     "dc_set_seed_schedule", "dc_clear_schedules", "dc_get_states", "dc_get_dxfixed", "dc_get_layout", "dc_get_packet_layout", "dc_get_bend_rows", "dc_comm_unique_id", "dc_comm_init", "dc_allreduce_sum", "dc_comm_destroy",
     "dc_get_deflation", "dc_set_record", "dc_set_trajectory_start", "dc_keep_force_gradients", "dc_get_force_gradients", "dc_use_stream", "dc_set_state_dev", "dc_get_state_dev", "dc_step_forward_dev", "dc_step_backward_dev",
     "dc_get_self_friction_path", "dc_get_adjoint_matrix", "dc_dense_phase_times", "dc_set_adjoint_band", "dc_get_adjoint_band",
@@ -725,6 +725,12 @@ class Engine:
         k = C.c_int(); nb = C.c_int()
         self._chk(self.lib.dc_get_cluster(self.h, C.byref(k), C.byref(nb)))
         return k.value
+
+    def cluster_rows(self):
+        """(rows per part, halo rows) of the split (dc_get_cluster_rows): part p owns device rows [p R, (p + 1) R); (0, 0) without a split"""
+        r = C.c_int(); hb = C.c_int()
+        self._chk(self.lib.dc_get_cluster_rows(self.h, C.byref(r), C.byref(hb)))
+        return r.value, hb.value
 
     def self_friction_path(self, reset=False):
         """[B, 2] per rollout since alloc_batch (or the last reset): PD iterations of the split forward kernel that ran a layered self-friction pass, and

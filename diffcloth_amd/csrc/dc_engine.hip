@@ -2199,6 +2199,13 @@ int dc_get_cluster(const dc_ctx *c, int *workgroups_per_rollout, int *rollouts_p
   return DC_OK;
 }
 
+int dc_get_cluster_rows(const dc_ctx *c, int *rows_per_part, int *halo_rows) {
+  if (!c) return DC_ERR_INVALID;
+  if (rows_per_part) *rows_per_part = c->cl.ok ? c->cl.D.R : 0;
+  if (halo_rows) *halo_rows = c->cl.ok ? c->cl.D.HB : 0;
+  return DC_OK;
+}
+
 int dc_get_self_friction_path(dc_ctx *c, int *out, int reset) {
   if (!c || !out) return DC_ERR_INVALID;
   std::memset(out, 0, sizeof(int) * 2 * (size_t) std::max(c->B, 0));

@@ -512,6 +512,10 @@ int dc_sync(dc_ctx *ctx);
  * and the device (environment DC_CLUSTER=k forces k; 0 or 1 = one workgroup per rollout). Results agree with the one-workgroup
  * kernels to solver tolerance (different summation order), not bitwise. Reports K and how many rollouts one launch covers. */
 int dc_get_cluster(const dc_ctx *ctx, int *workgroups_per_rollout, int *rollouts_per_launch);
+/* Rows of the split: part p of a rollout owns device rows [p * rows_per_part, (p + 1) * rows_per_part) — vertex i of a mesh that was not
+ * renumbered (dc_get_layout) belongs to part i / rows_per_part — and exchanges halo_rows boundary rows with each neighbour. 0, 0 with one
+ * workgroup per rollout. Read-only.                                                                                                     */
+int dc_get_cluster_rows(const dc_ctx *ctx, int *rows_per_part, int *halo_rows);
 /* Which path the split forward kernel took for the layered self friction (Simulation.cpp:655-678), counted per rollout since dc_alloc_batch
  * (or the last reset): out[2 b] = PD iterations that ran a self-friction pass, out[2 b + 1] = those of them in which every part evaluated the
  * layers itself (the parts share an XCD and the working set fits the LDS; DC_SELF_REDUNDANT=0 turns it off) instead of part 0 alone. All zero

@@ -61,8 +61,8 @@ class LandingScene(pv.Scene):
     may take mu times that, and the oracle's static and rotating spheres are 7.9e-3 ... 1.0e-2 apart after ONE step from the same state
     (measured on the oracle alone, every rollout and step of this scene): more than 100 forward gates."""
 
-    def __init__(self, spheres, W, D, steps=2, fall=FALL):
-        self.V, self.F = meshes.grid_cloth(17, 17, 4.5, 4.5, "DOWN")
+    def __init__(self, spheres, W, D, steps=2, fall=FALL, nx=17, threads=1):
+        self.V, self.F = meshes.grid_cloth(nx, nx, 4.5, 4.5, "DOWN")
         self.V = f32(self.V)
         self.N = N = self.V.shape[0]
         self.c0 = f32(meshes.sphere_scene_center(self.V, 2.0))
@@ -80,7 +80,7 @@ class LandingScene(pv.Scene):
         self.Xe = np.zeros((steps, self.nb, 3 * N)); self.Ve = np.zeros_like(self.Xe)
         self.XFe = np.zeros((steps, self.nb, 0))
         for b in range(self.nb):
-            o = orc.Oracle(self.V, self.F, h=H, fwd_tol=1e-9, bwd_tol=1e-9, selfcollision=False, gradient_clipping=False, **pv.FABRIC)
+            o = orc.Oracle(self.V, self.F, h=H, fwd_tol=1e-9, bwd_tol=1e-9, selfcollision=False, gradient_clipping=False, threads=threads, **pv.FABRIC)
             for g, (c, rot) in enumerate(self.spheres):
                 o.add_sphere(f32(c + self.D[b, g]), self.prims[g]["radius"], self.prims[g]["mu"], rotates=bool(rot))
             o.build()
@@ -498,6 +498,14 @@ def test_kernel_families_selected_at_build(name, monkeypatch):
     assert not (lay["dense_inverse"] if name == "DC_DENSE_MAX_N" else lay["element_windows"])
     e.close()
     run_parity("rotating", backward=False)
+
+
+@pytest.mark.parametrize("name", ["DC_DENSE_MAX_N", "DC_WINDOWS"])
+def test_gradients_under_the_kernel_families_selected_at_build(name, monkeypatch):
+    """the records those forward kernels leave, differentiated: two steps, backward and injected checks. DC_WINDOWS=0 also puts the one adjoint
+    instance without element windows under a velocity and spin table."""
+    monkeypatch.setenv(name, "0")
+    run_parity("rotating", steps=2, backward=True)
 
 
 @pytest.mark.parametrize("variant", ["global", "0", "1"])

@@ -47,13 +47,13 @@ W1 = np.array([[0.0, 0.0, 0.0], [2.0, -1.0, -0.5], [-4.0, 0.0, 2.0], [1.0, 1.0, 
 D1 = np.array([[0.0, 0.125, 0.0], [0.25, 0.1875, 0.125], [0.0, 0.125, 0.0], [0.0, -4.0, 0.0]]).reshape(B, 1, 3)      # (b0, b1, b3: offsets of that scene)
 
 
-def make_engine(V, F, prims, att=(), mode=1, selfcollision=0, fabric=FABRIC, tight=True):
+def make_engine(V, F, prims, att=(), mode=1, selfcollision=0, fabric=FABRIC, tight=True, cg_max_iter=2000):
     e = capi.Engine(0)
     e.set_mesh(V, F)
     e.set_attachments(att)
     tol = dict(forward_tol=1e-9, backward_tol=1e-9, cg_rel_tol=1e-6, adjoint_rel_tol=1e-8) if tight else \
         dict(forward_tol=1e-7, backward_tol=1e-7, cg_rel_tol=1e-5, adjoint_rel_tol=1e-7)
-    e.set_params(time_step=H, cg_max_iter=2000, gradient_clipping=0, selfcollision_enabled=selfcollision, adjoint_mode=mode, **fabric, **tol)
+    e.set_params(time_step=H, cg_max_iter=cg_max_iter, gradient_clipping=0, selfcollision_enabled=selfcollision, adjoint_mode=mode, **fabric, **tol)
     e.set_primitives(prims)
     e.build()
     return e
@@ -71,8 +71,8 @@ class Scene:
     """Mesh, spheres [(centre, rotates)], per-rollout velocities W [B][G][3] and centre offsets D [B][G][3], attachments; and the oracle's
     teacher-forced trajectory in the static frame with everything the tests compare against, computed once (CPU, fp64)."""
 
-    def __init__(self, spheres, W, D, att=(), steps=S):
-        self.V, self.F = meshes.grid_cloth(17, 17, 4.5, 4.5, "DOWN")
+    def __init__(self, spheres, W, D, att=(), steps=S, nx=17, threads=1):
+        self.V, self.F = meshes.grid_cloth(nx, nx, 4.5, 4.5, "DOWN")
         self.V = f32(self.V)
         self.N = self.V.shape[0]
         self.c0 = f32(meshes.sphere_scene_center(self.V, 2.0))
@@ -93,7 +93,7 @@ class Scene:
         self.XFe = np.zeros((steps, self.nb, 3 * len(self.att)))
         for b in range(self.nb):
             o = orc.Oracle(self.V, self.F, h=H, fwd_tol=1e-9, bwd_tol=1e-9, selfcollision=False, gradient_clipping=False,
-                           attachments=list(self.att), **FABRIC)
+                           attachments=list(self.att), threads=threads, **FABRIC)
             for g, (c, rot) in enumerate(self.spheres):
                 o.add_sphere(f32(c + self.D[b, g]), 2.0, 0.4, rotates=bool(rot))
             o.build()
@@ -505,6 +505,14 @@ def test_kernel_families_selected_at_build(name, monkeypatch):
     assert not (lay["dense_inverse"] if name == "DC_DENSE_MAX_N" else lay["element_windows"])
     e.close()
     run_parity("base", backward=False)
+
+
+@pytest.mark.parametrize("name", ["DC_DENSE_MAX_N", "DC_WINDOWS"])
+def test_gradients_under_the_kernel_families_selected_at_build(name, monkeypatch):
+    """the records those forward kernels leave, differentiated: two steps, backward and injected checks. DC_WINDOWS=0 also puts the one adjoint
+    instance without element windows under a velocity table."""
+    monkeypatch.setenv(name, "0")
+    run_parity("base", steps=2, backward=True)
 
 
 @pytest.mark.parametrize("variant", ["global", "0", "1"])
