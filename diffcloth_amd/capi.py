@@ -73,6 +73,7 @@ EXPORTED_SYMBOLS = [
     "dc_get_primitive_spins", "dc_get_primitive_spin_gradients", "dc_get_primitive_spin_gradients_dev",
     "dc_set_primitive_shapes", "dc_set_primitive_shape_schedule", "dc_set_primitive_shapes_dev", "dc_set_primitive_shape_schedule_dev",
     "dc_get_primitive_shapes",
+    "dc_get_contact_readout", "dc_get_contact_readout_dev",
 ]
 
 _lib = None
@@ -408,6 +409,45 @@ class Engine:
         g = np.zeros((self.B, self.N), dtype=np.int32); n = np.zeros((self.B, 3 * self.N))
         self._chk(self.lib.dc_get_contacts(self.h, C.c_int(slot), _i(g), _d(n)))
         return g, n
+
+    def _readout_range(self, slot0, nslots):
+        slot0, nslots = int(slot0), int(nslots)
+        if slot0 < 1:
+            raise ValueError("contact_readout: slot 0 has no record (slot0 >= 1)")
+        if nslots < 1:
+            raise ValueError("contact_readout: nslots must be >= 1")
+        return slot0, nslots
+
+    def contact_readout(self, slot0, nslots=1, state=True, normal_impulse=True, wrench=True):
+        """dc_get_contact_readout of the records slot0 .. slot0 + nslots - 1: dict(state [nslots][B][N] int32 — 0 not in primitive contact,
+        1 take-off, 2 stick, 3 slide —, normal_impulse [nslots][B][N], wrench [nslots][B][G][10] = {J[3], tau[3], sum jn, take-off, stick,
+        slide counts} per primitive group; J is the momentum handed to the obstacle in the step, J / time_step the mean force). Each output
+        can be switched off (its entry is then None); the call synchronises."""
+        slot0, nslots = self._readout_range(slot0, nslots)
+        if not (state or normal_impulse or wrench):
+            raise ValueError("contact_readout: nothing asked for")
+        s = np.zeros((nslots, self.B, self.N), dtype=np.int32) if state else None
+        j = np.zeros((nslots, self.B, self.N)) if normal_impulse else None
+        w = np.zeros((nslots, self.B, self.ngroups, 10)) if wrench else None
+        self._chk(self.lib.dc_get_contact_readout(self.h, C.c_int(slot0), C.c_int(nslots), _i(s), _d(j), _d(w)))
+        return dict(state=s, normal_impulse=j, wrench=w)
+
+    def contact_readout_dev(self, slot0, nslots, state=None, normal_impulse=None, wrench=None):
+        """dc_get_contact_readout_dev into CUDA tensors: state int32 [nslots][B][N], normal_impulse [nslots][B][N] and wrench
+        [nslots][B][G][10] of one floating dtype; None skips an output. Only enqueued on the context's stream."""
+        import torch
+        slot0, nslots = self._readout_range(slot0, nslots)
+        if state is None and normal_impulse is None and wrench is None:
+            raise ValueError("contact_readout_dev: nothing asked for")
+        ps = None
+        if state is not None:
+            if not state.is_cuda or not state.is_contiguous() or state.dtype != torch.int32 or state.numel() != nslots * self.B * self.N:
+                raise ValueError(f"state: expected a contiguous CUDA int32 tensor of {nslots * self.B * self.N} elements, got {state.dtype} {tuple(state.shape)} on {state.device}")
+            if state.device.index != self.device:
+                raise ValueError(f"tensor on cuda:{state.device.index}, the engine runs on device {self.device}")
+            ps = C.c_void_p(state.data_ptr())
+        (pj, pw), f = self._tps((normal_impulse, self.B * self.N, nslots), (wrench, self.B * self.ngroups * 10, nslots))
+        self._chk(self.lib.dc_get_contact_readout_dev(self.h, C.c_int(slot0), C.c_int(nslots), ps, pj, pw, C.c_int(f)))
 
     def get_self_contacts(self, slot, rollout=0, cap=8192):
         cnt = C.c_int(); nl = C.c_int()

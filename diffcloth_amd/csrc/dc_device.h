@@ -30,6 +30,8 @@ constexpr int kMetaStride = 4096;
 
 // floats per primitive group in a row of the obstacle-motion table (FwdArgs::pvel, BwdArgs::pvel / d_pvel): {w[3], omega[3]}
 constexpr int kPvRow = 6;
+// values per (slot, rollout, primitive group) of the contact read-out's sums (dc_get_contact_readout): {J[3], tau[3], sum jn, take-off, stick, slide}
+constexpr int kWrenchRow = 10;
 
 struct DevPrim {
   int kind, group, rotates, pad;
@@ -282,6 +284,10 @@ void launch_copy_cast_half(const float *src, void *dst, int is_f32, long rows, i
 void launch_prim_centres(const double *built, const int *group_of_prim, const void *d, int is_f32, float *dst, long rows, int P, int G, hipStream_t st);
 void launch_dfu_from_param(const float *dpar, void *out, int is_f32, long rows, hipStream_t st);
 void launch_dfv_scale(const float *ys, const float *fv, void *out, int is_f32, int nslots, int B, int N, double h2, hipStream_t st);
+// contact read-out of `rows` = slots x rollouts consecutive records in ONE launch (dc_readout.hip); every pointer is that of the first row, PV null
+// while no motion table exists; state (int32, [rows][N]), jn ([rows][N]) and wrench ([rows][G][kWrenchRow]) are each optional
+void launch_contact_readout(const DevSystem &S, const float *X, const float *F, const float *NRM, const int *PRIM, const float *PC, const float *PV,
+                            const float *mu, long rows, int B, int *state, void *jn, void *wrench, int is_f32, hipStream_t st);
 void launch_dfv(const float *ys, const float *w, void *out, int is_f32, int nslots, int B, int N, const int *user_of, double h2, hipStream_t st);
 
 }  // namespace dc

@@ -92,6 +92,16 @@ __device__ __forceinline__ f3 dry_friction(f3 n, f3 d, float mu) {
   if (nT <= mu * fabsf(sd)) return r - dT;                 // stick
   return r - dT * (mu * fabsf(sd) / nT);                   // slide
 }
+// Which branch dry_friction(n, d, mu) takes, with its own comparisons on its own expressions: 1 = take-off (sd = d.n >= 0), 2 = stick
+// (|dT| <= mu |sd|), 3 = slide. The public contact state of dc_get_contact_readout (0 = not in primitive contact is the caller's);
+// the reference's CollisionType + 1.
+__device__ __forceinline__ int contact_state(f3 n, f3 d, float mu) {
+  float sd = dot(d, n);
+  if (sd >= 0.f) return 1;
+  f3 dN = n * sd, dT = d - dN;
+  float nT = sqrtf(dot(dT, dT));
+  return nT <= mu * fabsf(sd) ? 2 : 3;
+}
 // w = J^T u with J = dr/dd of the same contact: Simulation::calculatedri_dfi (Simulation.cpp:881-919), applied
 // matrix-free. take-off: 0; stick: -u; slide: J = -n n^T + mu (b (I - a a^T)/|dT| (I - n n^T) + a n^T).
 __device__ __forceinline__ f3 dri_dfi_T(f3 n, f3 d, float mu, f3 u) {

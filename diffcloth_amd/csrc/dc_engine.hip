@@ -2124,6 +2124,58 @@ int dc_get_force_schedule_gradients_dev(dc_ctx *c, int slot0, int nslots, void *
   return DC_OK;
 }
 
+// ---- contact read-out (dc_readout.hip): state, normal impulse and per-group wrench rows of the records slot0 .. slot0 + nslots - 1
+namespace {
+int readout_check(dc_ctx *c, const char *who, int slot0, int nslots, const void *state, const void *jn, const void *wrench) {
+  if (!c) return DC_ERR_INVALID;
+  const std::string w(who);
+  if (slot0 < 1) return fail(c, DC_ERR_INVALID, w + ": slot 0 has no record");
+  if (nslots < 1) return fail(c, DC_ERR_INVALID, w + ": nslots < 1");
+  if (!state && !jn && !wrench) return fail(c, DC_ERR_INVALID, w + ": state, normal_impulse and wrench are all null");
+  if (!c->built) return fail(c, DC_ERR_STATE, "dc_build has not been called");
+  if (wrench && c->ngroups < 1) return fail(c, DC_ERR_INVALID, w + ": wrench asked of a context with no primitive group");
+  if (c->B > 0 && (long) slot0 + nslots - 1 > c->tape) return fail(c, DC_ERR_INVALID, w + ": slots " + std::to_string(slot0) + " .. " + std::to_string((long) slot0 + nslots - 1) + " reach past the tape of " + std::to_string(c->tape) + " steps");
+  return check_batch(c, slot0, slot0 + nslots - 1);
+}
+void readout_enqueue(dc_ctx *c, int slot0, int nslots, int *state, void *jn, void *wrench, int is_f32) {
+  const size_t se = slot_elems(c), sp = (size_t) c->B * c->host.N;
+  launch_contact_readout(c->S, c->X + se * slot0, c->F + se * slot0, c->NRM + se * slot0, c->PRIM + sp * slot0, pc_slot(c, slot0),
+                         c->PV ? pv_slot(c, slot0) : nullptr, c->mu, (long) nslots * c->B, c->B, state, jn, wrench, is_f32, c->stream);
+}
+// device memory of one host-form call, freed when the call returns
+struct ReadoutStage {
+  void *p = nullptr;
+  ~ReadoutStage() { if (p) (void) hipFree(p); }
+};
+}  // namespace
+
+int dc_get_contact_readout_dev(dc_ctx *c, int slot0, int nslots, void *d_state, void *d_normal_impulse, void *d_wrench, int is_f32) {
+  int rc = readout_check(c, "dc_get_contact_readout_dev", slot0, nslots, d_state, d_normal_impulse, d_wrench);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  readout_enqueue(c, slot0, nslots, (int *) d_state, d_normal_impulse, d_wrench, is_f32);
+  HIPCHK(c, hipGetLastError());
+  return DC_OK;
+}
+
+int dc_get_contact_readout(dc_ctx *c, int slot0, int nslots, int *state, double *normal_impulse, double *wrench) {
+  int rc = readout_check(c, "dc_get_contact_readout", slot0, nslots, state, normal_impulse, wrench);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t nv = (size_t) nslots * c->B * c->host.N, nw = (size_t) nslots * c->B * c->ngroups * kWrenchRow;
+  ReadoutStage ds, dj, dw;
+  if (state) HIPCHK(c, hipMalloc(&ds.p, nv * sizeof(int)));
+  if (normal_impulse) HIPCHK(c, hipMalloc(&dj.p, nv * sizeof(double)));
+  if (wrench) HIPCHK(c, hipMalloc(&dw.p, nw * sizeof(double)));
+  readout_enqueue(c, slot0, nslots, (int *) ds.p, dj.p, dw.p, 0);
+  HIPCHK(c, hipGetLastError());
+  if (state) HIPCHK(c, hipMemcpyAsync(state, ds.p, nv * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (normal_impulse) HIPCHK(c, hipMemcpyAsync(normal_impulse, dj.p, nv * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (wrench) HIPCHK(c, hipMemcpyAsync(wrench, dw.p, nw * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return cluster_check(c);
+}
+
 int dc_set_mu_dev(dc_ctx *c, const void *d_mu, int is_f32) {
   int rc = check_batch(c, 0, 0);
   if (rc) return rc;

@@ -84,6 +84,39 @@ class BatchedSim:
                 raise RuntimeError(msg)
             warnings.warn(msg, RuntimeWarning, stacklevel=2)
 
+    def contact_readout(self, slot0=1, nslots=None, dtype=torch.float32, state=True, normal_impulse=True, wrench=True):
+        """What the obstacles feel in the steps of this episode (dc_get_contact_readout_dev): CUDA tensors of the records slot0 ..
+        slot0 + nslots - 1 (nslots None: up to the last step taken), formed on the engine's GPU on torch's current stream, without a
+        synchronisation. Usable after sim_step and after a sim_rollout forward pass.
+          state           int32 [nslots, B, N]: 0 not in primitive contact, 1 take-off, 2 stick, 3 slide
+          normal_impulse  [nslots, B, N]: r_p . n of the primitive part of the contact response
+          wrench          [nslots, B, G, 10] per primitive group: J[3] = -sum r_p (momentum handed to the obstacle in the step; J / time_step is
+                          the mean force), tau[3] about the centre of the group's first primitive in that step, sum of the normal impulses,
+                          take-off / stick / slide counts
+        An output switched off (or, for wrench, a scene without primitives) is None. The outputs carry NO gradient (requires_grad is False):
+        they are observations, not differentiable functions of the inputs."""
+        e = self.engine
+        slot0 = int(slot0)
+        if slot0 < 1:
+            raise ValueError("contact_readout: slot 0 has no record (slot0 >= 1)")
+        if nslots is None:
+            nslots = self.step_idx - slot0 + 1
+        nslots = int(nslots)
+        if nslots < 1 or slot0 + nslots - 1 > self.step_idx:
+            raise ValueError(f"contact_readout: records {slot0} .. {slot0 + nslots - 1} asked for, the episode has taken {self.step_idx} step(s)")
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("contact_readout: dtype must be torch.float32 or torch.float64")
+        wrench = bool(wrench) and e.ngroups > 0
+        if not (state or normal_impulse or wrench):
+            raise ValueError("contact_readout: nothing asked for")
+        dev = torch.device("cuda", e.device)
+        self.on_current_stream(dev)
+        s = torch.empty((nslots, e.B, e.N), dtype=torch.int32, device=dev) if state else None
+        j = torch.empty((nslots, e.B, e.N), dtype=dtype, device=dev) if normal_impulse else None
+        w = torch.empty((nslots, e.B, e.ngroups, 10), dtype=dtype, device=dev) if wrench else None
+        e.contact_readout_dev(slot0, nslots, s, j, w)
+        return dict(state=s, normal_impulse=j, wrench=w)
+
     def reset(self, x0, v0=None):
         """Start a new episode from the given states ([B, 3N]); returns them as float32 tensors like getStateInfo()."""
         if self.step_idx > 0:

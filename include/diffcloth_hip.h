@@ -493,6 +493,28 @@ int dc_get_dxfixed_dev(dc_ctx *ctx, int slot0, int nslots, void *d_dL_dxfixed /*
  * Sums are accumulated in fp64 in a fixed order without atomics and rounded once: bit-reproducible from run to run.                  */
 int dc_get_force_schedule_gradients_dev(dc_ctx *ctx, int slot0, int nslots, void *d_dL_dfu /*nslots*B*3 or NULL*/,
                                         void *d_dL_dfv_scale /*nslots*B or NULL*/, void *d_dL_dfv /*B*3N or NULL*/, int is_f32);
+/* Contact read-out: what the obstacles feel. For the records slot0 .. slot0 + nslots - 1 (slot0 >= 1) ONE kernel launch on the context's stream
+ * re-forms, per vertex in primitive contact, the friction law's argument exactly as the step did — d = f - m (v_rot + w + v_spin), n and f from the
+ * fp32 record `slot`, the motion row {w, omega} of `slot` (the step that produced it), mu = the context's CURRENT mu[b][group], as the backward
+ * step reads it — and reports
+ *   state[k][b][i]            0 = vertex i not in primitive contact, 1 = take-off, 2 = stick, 3 = slide (CollisionType + 1 of the reference), by the
+ *                             comparisons of the friction law itself: sd = d.n >= 0 -> take-off, else |dT| <= mu |sd| -> stick, else slide
+ *   normal_impulse[k][b][i]   jn = r_p . n >= 0, r_p = r(d) the PRIMITIVE part of the step's r (the stored r of dc_get_record also holds what
+ *                             the self-contact layers added afterwards); 0 where state is 0 or 1
+ *   wrench[k][b][g][0..9]     per primitive group g: J[3] = -sum r_p, the momentum handed to the obstacle during the step (the mean force
+ *                             is J / time_step); tau[3] = -sum (x_i - c_g) x r_p, x_i the state of `slot`, c_g the centre of the group's FIRST
+ *                             flattened primitive in that step (dc_get_primitive_centers: an offset schedule moves the reference point with
+ *                             the obstacle); sum jn; the numbers of take-off, stick and slide contacts. A group without contacts: zeros.
+ * Per-vertex outputs are in the caller's vertex numbering. Sums run in fp64 in a fixed order without atomics and are rounded once:
+ * bit-reproducible. Each output may be NULL and is then not computed; all three NULL is DC_ERR_INVALID, as are slot0 < 1, nslots < 1, a
+ * range past the tape, and a wrench pointer on a context with no primitive group. A record handed in with dc_set_record is read like any
+ * other (its fp32 values). The outputs carry no derivative.
+ * The host form copies back through device buffers of its own and synchronises. The _dev form only enqueues: d_state is int32, the other two
+ * fp32 (is_f32 = 1) or fp64; nothing crosses PCIe.                                                                                   */
+int dc_get_contact_readout(dc_ctx *ctx, int slot0, int nslots, int *state /*nslots*B*N or NULL*/,
+                           double *normal_impulse /*nslots*B*N or NULL*/, double *wrench /*nslots*B*num_groups*10 or NULL*/);
+int dc_get_contact_readout_dev(dc_ctx *ctx, int slot0, int nslots, void *d_state /*int32, nslots*B*N or NULL*/, void *d_normal_impulse /*nslots*B*N or NULL*/,
+                               void *d_wrench /*nslots*B*num_groups*10 or NULL*/, int is_f32);
 /* dc_set_mu (d_mu must not be NULL: dc_set_mu(NULL) restores the defaults) and dc_set_vertex_forces (NULL = none) from device buffers */
 int dc_set_mu_dev(dc_ctx *ctx, const void *d_mu /*B*num_groups*/, int is_f32);
 int dc_set_vertex_forces_dev(dc_ctx *ctx, const void *d_f /*B*3N or NULL*/, int is_f32);
