@@ -61,7 +61,7 @@ EXPORTED_SYMBOLS = [
     "dc_timer_stop", "dc_kernel_times", "dc_get_cluster", "dc_get_cluster_rows", "dc_set_gradient", "dc_set_fixed_point_schedule", "dc_set_force_schedule",
     "dc_set_seed_schedule", "dc_clear_schedules", "dc_get_states", "dc_get_dxfixed", "dc_get_layout", "dc_get_packet_layout", "dc_get_bend_rows", "dc_comm_unique_id", "dc_comm_init", "dc_allreduce_sum", "dc_comm_destroy",
     "dc_get_deflation", "dc_set_record", "dc_set_trajectory_start", "dc_keep_force_gradients", "dc_get_force_gradients", "dc_use_stream", "dc_set_state_dev", "dc_get_state_dev", "dc_step_forward_dev", "dc_step_backward_dev",
-    "dc_get_self_friction_path", "dc_get_adjoint_matrix", "dc_dense_phase_times", "dc_set_adjoint_band", "dc_get_adjoint_band",
+    "dc_get_self_friction_path", "dc_get_adjoint_contact_path", "dc_get_adjoint_matrix", "dc_dense_phase_times", "dc_set_adjoint_band", "dc_get_adjoint_band",
     "dc_rollout_forward_async", "dc_rollout_backward_async", "dc_set_fixed_point_schedule_dev", "dc_set_force_schedule_dev", "dc_set_seed_schedule_dev",
     "dc_set_gradient_dev", "dc_get_gradient_dev", "dc_get_states_dev", "dc_get_dxfixed_dev", "dc_get_force_schedule_gradients_dev", "dc_set_mu_dev",
     "dc_set_vertex_forces_dev",
@@ -777,6 +777,13 @@ class Engine:
         those of them in which every part evaluated the layers itself (dc_get_self_friction_path); zeros with one workgroup per rollout"""
         out = np.zeros((self.B, 2), dtype=np.int32)
         self._chk(self.lib.dc_get_self_friction_path(self.h, _i(out), C.c_int(int(reset))))
+        return out
+
+    def adjoint_contact_path(self, reset=False):
+        """[B, 2] per rollout since alloc_batch (or the last reset): backward steps run by an adjoint instance that can hold the step's contact
+        tables in LDS, and those of them that used the tables (dc_get_adjoint_contact_path); zeros for every other instance"""
+        out = np.zeros((self.B, 2), dtype=np.int32)
+        self._chk(self.lib.dc_get_adjoint_contact_path(self.h, _i(out), C.c_int(int(reset))))
         return out
 
     def timer_start(self):

@@ -141,6 +141,31 @@ struct AdjCtx {
   // one bit per vertex, mark[i] != 0, in LDS at the end of the list's room (k_adjoint_step builds it once per step; null when list and mask do not
   // both fit, or without bending rows): how the per-vertex phase of the CG's operator learns that its own staged slot holds y_i and not z_i
   const unsigned *cmask;
+  // the step-resident contact tables (ResTab below) in LDS under the mask, built once per step by the instances that have the mask, when list, mask
+  // and tables all fit: the operator's contact phase then reads everything but z from LDS, and the list is ordered by vertex index — a contact
+  // vertex's slot is its rank among the set bits of cmask (adj_rank, dc_launchplan.h), not what its mark names. Null: the path without them.
+  int rtab;      // float index from lds, 0 = none
+};
+
+// Views into the tables (layout: adj_tables_floats, dc_launchplan.h). Every input of the contact phase that is constant over a backward step:
+// what self_JT_layers_lds_v stages per application (normals with their two slots, d, 1 / mass per working-set slot, layer offsets) with the slot ->
+// vertex table (bit 31: the vertex is in contact with a primitive too, whose entry then owns its slot), and per primitive-contact vertex the
+// vertex, its working-set slot (-1: none) and the inputs of dri_dfi_T — n, d = prim_d(...), mu: the same functions are evaluated per application.
+struct ResTab {
+  int nc, nl, M, np;
+  const float4 *ln, *ld;
+  const float *lim;
+  const int *sv, *loff, *pv, *pss;
+  const float *pn, *pd, *pmu;      // pn, pd: three planes of np
+  __device__ __forceinline__ ResTab(const float *t, int M_, int np_) {
+    const int *h = (const int *) t;
+    nc = h[0]; nl = h[1]; M = M_; np = np_;
+    ln = (const float4 *) (t + 4); ld = ln + nc;
+    lim = (const float *) (ld + nc);
+    sv = (const int *) (lim + M); loff = sv + M;
+    pv = loff + nl + 1; pss = pv + np;
+    pn = (const float *) (pss + np); pd = pn + 3 * np; pmu = pd + 3 * np;
+  }
 };
 
 // w = dr_df^T z for the (block-diagonal) primitive contacts: Simulation::calculatedr_df (Simulation.cpp:700-711)
@@ -194,6 +219,124 @@ __device__ __forceinline__ void contact_transpose(const DevSystem &S, const AdjC
         if (i < N) st3(y, i, N, zq[j] + w);
       }
     }
+  }
+  __syncthreads();
+}
+
+// Once per backward step, after plist / mark / cmask: the per-word counts of the mask (`pf`, the mwords words under it) and the tables at `tab`.
+// All threads call; ends with a barrier.
+template <int THREADS>
+__device__ __forceinline__ void build_contact_tables(const DevSystem &S, const AdjCtx &C, float *tab, int nc, int nl) {
+  const int N = S.N, tid = threadIdx.x;
+  const int mwords = adj_mask_words(N), M = C.nself_verts, np = C.nplist;
+  const unsigned *cm = C.cmask;
+  unsigned *pf = (unsigned *) cm - mwords;
+  // (a thread per word sums the words before it: a few hundred independent LDS reads once per step, no scratch)
+#pragma unroll 1
+  for (int w = tid; w < mwords; w += THREADS) {
+    unsigned before = 0;
+#pragma unroll 1
+    for (int k = 0; k < w; k++) before += __popc(cm[k]);
+    pf[w] = before;
+  }
+  int *h = (int *) tab;
+  if (tid == 0) { h[0] = nc; h[1] = nl; h[2] = 0; h[3] = 0; }
+  float4 *ln = (float4 *) (tab + 4), *ld = ln + nc;
+  float *lim = (float *) (ld + nc);
+  int *sv = (int *) (lim + M), *loff = sv + M, *pv = loff + nl + 1, *pss = pv + np;
+  float *pn = (float *) (pss + np), *pd = pn + 3 * np, *pmu = pd + 3 * np;
+  for (int q = tid; q < np; q += THREADS) {
+    const int i = C.plist[q], prim = C.rec_prim[i];
+    const f3 n = ld3(C.rec_n, i, N);
+    const f3 d = prim_d(S.prims[prim], n, ld3(C.rec_f, i, N), S.mass[i], DC_ADJ_PVEL(C));
+    pv[q] = i; pss[q] = -1;
+    pn[q] = n.x; pn[np + q] = n.y; pn[2 * np + q] = n.z;
+    pd[q] = d.x; pd[np + q] = d.y; pd[2 * np + q] = d.z;
+    pmu[q] = C.mu[S.prims[prim].group];
+  }
+  __syncthreads();
+  if (M > 0) {
+    const int cap = S.self_cap;
+    const int *meta = C.self.meta + (size_t) C.b * kMetaStride;
+    const float4 *nrm = C.self.nrm + (size_t) C.b * cap, *dvec = C.self.dvec + (size_t) C.b * cap;
+    const int *verts = C.self.verts + (size_t) C.b * 2 * cap;
+    for (int s = tid; s < M; s += THREADS) {
+      const int v = verts[s], m = C.mark[v];
+      lim[s] = 1.0f / S.mass[v];
+      sv[s] = (m & 2) ? (v | (int) 0x80000000) : v;
+      if (m & 2) pss[m >> 2] = s;      // (the mark of a vertex with both kinds of contact names its position in plist)
+    }
+    for (int k = tid; k < nc; k += THREADS) { ln[k] = nrm[k]; ld[k] = dvec[k]; }
+    for (int l = tid; l <= nl; l += THREADS) loff[l] = meta[2 + l];
+  }
+  __syncthreads();
+}
+
+// The operator's contact phase from the tables: one gather of z (working set and primitive list together, indices from LDS), the layers walked in
+// the windows' LDS exactly as self_JT_layers_lds_v walks them, y_i of the primitive entries by the same dri_dfi_T from the resident (n, d, mu), the
+// list written by rank and y stored to C.y for its later readers. Same values, same order of the sums as the path without tables. Ends with a barrier.
+template <int THREADS>
+__device__ __forceinline__ void contact_phase_resident(const DevSystem &S, const AdjCtx &C, const float *zin) {
+  const int N = S.N, tid = threadIdx.x;
+  const ResTab T(C.lds + C.rtab, C.nself_verts, C.nplist);
+  const int M = T.M, np = T.np;
+  const unsigned *cm = C.cmask, *pf = cm - adj_mask_words(N);
+  float *lz = C.lds, *ylist = C.ylist;
+  for (int e = tid; e < M + np; e += THREADS) {
+    const int q = e - M;
+    if (q >= 0 && T.pss[q] >= 0) continue;      // (takes the working set's result below)
+    const int i = q < 0 ? (T.sv[e] & 0x7fffffff) : T.pv[q];
+    const f3 z = ld3(zin, i, N);
+    if (q < 0) { lz[e] = z.x; lz[M + e] = z.y; lz[2 * M + e] = z.z; }
+    else { float *yl = ylist + 3 * adj_rank(cm, pf, i); yl[0] = z.x; yl[1] = z.y; yl[2] = z.z; }
+  }
+  __syncthreads();
+  if (M > 0) {
+    auto contact = [&](int k) {
+      const float4 n4 = T.ln[k], d4 = T.ld[k];
+      const int sl = __float_as_int(n4.w), sa = sl & 0xffff, sb = sl >> 16;
+      const float iA = T.lim[sa], iB = T.lim[sb];
+      f3 zA = mk(lz[sa], lz[M + sa], lz[2 * M + sa]), zB = mk(lz[sb], lz[M + sb], lz[2 * M + sb]);
+      f3 g = dri_dfi_T(mk(n4.x, n4.y, n4.z), mk(d4.x, d4.y, d4.z), kClothMu, zA - zB) * (1.0f / (iA + iB));
+      zA = zA + g * iA; zB = zB - g * iB;
+      lz[sa] = zA.x; lz[M + sa] = zA.y; lz[2 * M + sa] = zA.z;
+      lz[sb] = zB.x; lz[M + sb] = zB.y; lz[2 * M + sb] = zB.z;
+    };
+    if (T.nl <= kWideLayers) {
+      for (int l = T.nl - 1; l >= 0; l--) {
+        const int k1 = T.loff[l + 1];
+        for (int k = T.loff[l] + tid; k < k1; k += THREADS) contact(k);
+        __syncthreads();
+      }
+    } else {
+      if (tid < 64) {
+        for (int l = T.nl - 1; l >= 0; l--) {
+          const int k1 = T.loff[l + 1];
+          for (int k = T.loff[l] + tid; k < k1; k += 64) contact(k);
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (int e = tid; e < M + np; e += THREADS) {
+    const int q = e - M;
+    int i;
+    f3 yv;
+    if (q < 0) {
+      i = T.sv[e];
+      if (i < 0) continue;      // (a vertex with both kinds of contact: the primitive's entry writes it)
+      yv = mk(lz[e], lz[M + e], lz[2 * M + e]);
+    } else {
+      i = T.pv[q];
+      const int ss = T.pss[q];
+      const float *yl = ylist + 3 * adj_rank(cm, pf, i);
+      const f3 z = ss >= 0 ? mk(lz[ss], lz[M + ss], lz[2 * M + ss]) : mk(yl[0], yl[1], yl[2]);
+      yv = z + dri_dfi_T(mk(T.pn[q], T.pn[np + q], T.pn[2 * np + q]), mk(T.pd[q], T.pd[np + q], T.pd[2 * np + q]), T.pmu[q], z);
+    }
+    float *yl = ylist + 3 * adj_rank(cm, pf, i);
+    yl[0] = yv.x; yl[1] = yv.y; yl[2] = yv.z;
+    st3(C.y, i, N, yv);
   }
   __syncthreads();
 }
@@ -284,7 +427,9 @@ struct SelfInOut {
 // Same operator with the element pass inside LDS (element windows, dc_winlib.h): no corner array, no atomics.
 // PRE: the per-vertex phase issues a vertex's global reads ahead of the gather (vert_with_pre, dc_winlib.h) — pays on the 10 000-vertex
 // cloth (12.95 -> 12.73 ms per batch step), costs the block-preconditioned garment kernels 36 B more scratch and 3 ... 8 % (they pass false)
-template <int THREADS, bool WIN, bool PRE>
+// RES (the CG's applications of the 1024-thread instances: no preconditioner): a step whose contact tables are resident (AdjCtx::rtab) takes
+// the contact phase from them and reads the list by rank; every other caller is compiled without that text
+template <int THREADS, bool WIN, bool PRE, bool RES = false>
 __device__ __forceinline__ void adjoint_operator(const DevSystem &S, const AdjCtx &C, const float *zin, bool precond,
                                                  float *out, const float *d1, float &dot1, float &dot2) {
   if constexpr (!WIN) { adjoint_operator_global<THREADS>(S, C, zin, precond, out, d1, dot1, dot2); return; }
@@ -340,10 +485,14 @@ __device__ __forceinline__ void adjoint_operator(const DevSystem &S, const AdjCt
   // and have no other sparse form: a step whose contact vertices do not fit the list (a sheet lying on a plane) forms y over all vertices below
   constexpr bool YL = THREADS == 1024;
   if constexpr (YL) sparse = sparse && C.ylist != nullptr;
-  if (sparse && C.nself > 0) sparse = self_JT_layers_lds_v<THREADS>(S, C.self, C.b, SelfInOut{zin, precond ? S.dinv : nullptr, C.y, N}, C.lds, C.lds_floats);   // ends with a barrier
+  bool res = false;
+  if constexpr (RES && YL) res = sparse && !precond && C.rtab != 0;      // (the tables' phase takes z as it is: no D^-1 scaling)
+  if (res) { if constexpr (RES && YL) contact_phase_resident<THREADS>(S, C, zin); }      // ends with a barrier
+  else if (sparse && C.nself > 0) sparse = self_JT_layers_lds_v<THREADS>(S, C.self, C.b, SelfInOut{zin, precond ? S.dinv : nullptr, C.y, N}, C.lds, C.lds_floats);   // ends with a barrier
   if (sparse) {
     const int *mark = C.mark;
     float *ylist = YL ? C.ylist : nullptr;
+    if (!res) {
     if (YL && C.nself > 0) {      // the self pass's working set is still in the windows' LDS ([3][M] planar at its start): its slots follow the primitives'
       const int M = C.nself_verts;
       float *yl = ylist + 3 * C.nplist;
@@ -359,8 +508,17 @@ __device__ __forceinline__ void adjoint_operator(const DevSystem &S, const AdjCt
       if constexpr (YL) { ylist[3 * q] = yv.x; ylist[3 * q + 1] = yv.y; ylist[3 * q + 2] = yv.z; }
     }
     __syncthreads();
+    }
     APH(0)
     auto stage_y = [&](int i) {
+      if constexpr (RES && YL) {
+        if (res) {                   // the slot is the vertex's rank among the mask's set bits: two LDS words, no load of mark[i]
+          const unsigned *cm = C.cmask;
+          f3 z = ld3(zin, i, N);
+          if ((cm[i >> 5] >> (i & 31)) & 1u) { const float *yl = ylist + 3 * adj_rank(cm, cm - adj_mask_words(N), i); z = mk(yl[0], yl[1], yl[2]); }
+          return z;
+        }
+      }
       const int m = mark[i];
       f3 z = ld3(zin, i, N);
       if (precond) z = z * S.dinv[i];
@@ -646,7 +804,7 @@ __device__ DC_OUTLINED Ret32 cg32_solve(const DevSystem &S, AdjCtx C, Krylov32 V
   // if the fp64 residual says it helped.
   for (int k = 2 * kdone; k < 2 * kcap && in_status == 0 && its < kCgCycleCap; k++) {
     // v = K p ;  alpha = (r . z) / (p . v)
-    adjoint_operator<THREADS, WIN, true>(S, C, p, false, v, p, d1, d2);
+    adjoint_operator<THREADS, WIN, true, THREADS == 1024 && WIN>(S, C, p, false, v, p, d1, d2);
     const double pv = krylov_sum<THREADS>(d1, redc);
     if (!(pv > 1e-300)) { in_status = 2; break; }      // not a descent direction in K's "energy": this system is not for CG
     const float alpha = (float) (rz / pv);
@@ -737,7 +895,7 @@ __global__ __launch_bounds__(THREADS) void k_adjoint_step(const DevSystem *__res
   C.nself = (S.contact_enabled && S.self_enabled) ? A.self.meta[(size_t) b * kMetaStride] : 0;
   // the contact vertices of this step (the detection's cell / order arrays are free during the backward sweep)
   C.mark = A.dense_y ? nullptr : W.sd_cell + (size_t) b * N;
-  C.plist = nullptr; C.nplist = 0; C.ylist = nullptr; C.nself_verts = 0; C.cmask = nullptr;
+  C.plist = nullptr; C.nplist = 0; C.ylist = nullptr; C.nself_verts = 0; C.cmask = nullptr; C.rtab = 0;
   if (C.mark) {
     int *plist = W.sd_order + (size_t) b * N;
     __shared__ int nplist;
@@ -772,7 +930,19 @@ __global__ __launch_bounds__(THREADS) void k_adjoint_step(const DevSystem *__res
         }
         C.cmask = cm;
         __syncthreads();
+        // the step-resident tables under the mask, when they fit as well (and the working set fits the windows' LDS, as the layered pass asks)
+        const int *meta = A.self.meta + (size_t) b * kMetaStride;
+        const int nc = C.nself > 0 ? min(meta[0], S.self_cap) : 0, nl = C.nself > 0 ? meta[1] : 0;
+        // (not for a step the operator forms y per vertex in the staging: no self contacts on a mesh of fewer than 4 windows, adjoint_operator)
+        if (adj_tables_fit(A.ycap, N, nplist, M, nc, nl, A.ytab) && (C.nself == 0 ? S.nwin >= 4 : (S.self_lds && self_lds_need(M, nc, nl) <= C.lds_floats))) {
+          float *tab = dyn_lds + ((A.ybase + 3 * A.ycap - 2 * mwords - adj_tables_floats(nplist, M, nc, nl)) & ~3);
+          build_contact_tables<THREADS>(S, C, tab, nc, nl);
+          C.rtab = (int) (tab - dyn_lds);
+        }
       }
+    }
+    if constexpr (WIN && THREADS == 1024 && !BLK && !COARSE) {
+      if (tid == 0 && A.adj_path) { A.adj_path[2 * b] += 1; A.adj_path[2 * b + 1] += C.rtab != 0; }      // (dc_get_adjoint_contact_path)
     }
   }
   float *gx = A.gx + off;

@@ -114,6 +114,7 @@ struct dc_ctx {
   int inj_slot = -1;
   dc_step_stats *fstats = nullptr;  // [(tape+1)][B]
   dc_bwd_stats *bstats = nullptr;   // [(tape+1)][B], indexed by the slot whose record was differentiated
+  int *adj_path = nullptr;          // [B][2] backward steps run by an instance with step-resident contact tables, and those that used them (dc_get_adjoint_contact_path)
   double *stage[4] = {nullptr, nullptr, nullptr, nullptr};   // staging of the host <-> device conversions, handed out by stage_take (dc_engine.hip)
   int stage_live = 0;               // how many of them have been handed out since the stream was last synchronised by stage_sync
   size_t stage_elems = 0;

@@ -237,6 +237,7 @@ struct BwdArgsStatic {
   int cg_first;                 // direct solve, diag(P) preconditioner: correction solves by CG, BiCGSTAB once a CG cycle fails to contract the fp64 residual (DC_ADJ_CG, default 1)
   int warm;                     // direct solve inside a fused sweep: start step s > 0 from gamma u*(step s - 1) (DC_ADJ_WARM, dc_adjoint.hip)
   int ycap, ybase;              // entries of the contact vertices' y list in the dynamic LDS and its start in floats (set by the launch: dc_adjoint.hip, AdjCtx::ylist)
+  int ytab;                     // floats of the list's room the step-resident contact tables may take (dc_adjoint.hip, AdjCtx::rtab): 0 = none (DC_ADJ_RESIDENT=0), capped by the test hook DC_TEST_YTAB_CAP
   // several consecutive steps of the backward sweep in one launch: step s differentiates tape slot `slot` - s
   int nsteps, slot;
   int start_at;                 // the record whose backward step is the trajectory's isStart step (dc_set_trajectory_start: start slot + 1; 0 = none)
@@ -246,6 +247,7 @@ struct BwdArgsStatic {
   // the self contacts' normals / d ([B][cap][3]) for the fp64 operator; all null for a record the forward kernels made
   const double *inj_x, *inj_f, *inj_n, *inj_sn, *inj_sd;
   float *ys;                    // y = (I + dr_df)^T u* of the step, kept per tape slot (dc_keep_force_gradients; steps by slot_state) or nullptr
+  int *adj_path;                // [B][2] counters of dc_get_adjoint_contact_path
 };
 
 struct BwdArgs : BwdArgsStatic {

@@ -216,11 +216,13 @@ BwdArgs bwd_args(dc_ctx *c, int slot, bool is_start, Seeds seeds) {
   A.warm = env_on("DC_ADJ_WARM", false);
   A.cg_first = env_on("DC_ADJ_CG", true);                                                     // (A/B switch: 0 = BiCGSTAB correction solves only)
   A.ycap = 0; A.ybase = 0;                                                                                    // (set by the launch, dc_adjoint.hip)
+  A.ytab = env_not_off("DC_ADJ_RESIDENT", true) ? std::max(env_int("DC_TEST_YTAB_CAP", 0x7fffffff), 0) : 0;      // (A/B switch; test hook: cap of the tables' floats)
   A.nsteps = 1; A.slot = slot;
   const bool inj = c->inj_slot == slot && c->INJ_X;
   A.inj_x = inj ? c->INJ_X : nullptr; A.inj_f = inj ? c->INJ_F : nullptr; A.inj_n = inj ? c->INJ_N : nullptr;
   A.inj_sn = inj ? c->INJ_SN : nullptr; A.inj_sd = inj ? c->INJ_SD : nullptr;
   A.ys = (c->keep_y && c->YS) ? c->YS + se * slot : nullptr;
+  A.adj_path = c->adj_path;
   A.pvel = c->PV ? pv_slot(c, slot) : nullptr; A.d_pvel = c->PV ? dpv_slot(c, slot) : nullptr; A.slot_pvel = c->PV ? pv_elems(c) : 0;
   A.slot_state = se; A.slot_prim = sp; A.slot_self = (size_t) c->B * c->self_cap; A.slot_meta = (size_t) c->B * kMetaStride;
   A.slot_param = (size_t) c->B * 8; A.slot_xf = xf_elems(c); A.slot_stats = (size_t) c->B;
@@ -1099,6 +1101,7 @@ int dc_alloc_batch(dc_ctx *c, int B, int tape) {
   if ((rc = dev_alloc(c, pool, &c->target, (size_t) 3 * N))) return rc;
   if ((rc = dev_alloc(c, pool, &c->fstats, (size_t) B * slots))) return rc;
   if ((rc = dev_alloc(c, pool, &c->bstats, (size_t) B * slots))) return rc;
+  if ((rc = dev_alloc(c, pool, &c->adj_path, 2 * (size_t) B))) return rc;
   c->stage_elems = se;
   for (int k = 0; k < 4; k++) if ((rc = dev_alloc(c, pool, &c->stage[k], se))) return rc;
   c->fu_set = false; c->fv_set = false; c->fv2_set = false;
@@ -2265,6 +2268,16 @@ int dc_get_self_friction_path(dc_ctx *c, int *out, int reset) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(out, c->cl.D.self_path, sizeof(int) * 2 * (size_t) c->B, hipMemcpyDeviceToHost));
   if (reset) HIPCHK(c, hipMemsetAsync(c->cl.D.self_path, 0, sizeof(int) * 2 * (size_t) c->B, c->stream));
+  return DC_OK;
+}
+
+int dc_get_adjoint_contact_path(dc_ctx *c, int *out, int reset) {
+  if (!c || !out) return DC_ERR_INVALID;
+  std::memset(out, 0, sizeof(int) * 2 * (size_t) std::max(c->B, 0));
+  if (!c->adj_path || c->B <= 0) return DC_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, c->adj_path, sizeof(int) * 2 * (size_t) c->B, hipMemcpyDeviceToHost));
+  if (reset) HIPCHK(c, hipMemsetAsync(c->adj_path, 0, sizeof(int) * 2 * (size_t) c->B, c->stream));
   return DC_OK;
 }
 

@@ -70,6 +70,25 @@ inline AdjYlist adj_ylist(int threads, size_t lds, size_t lds_limit, size_t stat
   return y;
 }
 
+// The tail of the list's room (3 * ycap floats from ybase), from its end backwards: the contact mask (one bit per vertex, adj_mask_words), one
+// count per mask word of the set bits in the words before it (the same number of words), and the step-resident contact tables of
+// adjoint_operator (dc_adjoint.hip). With the list ordered by vertex index a contact vertex's slot is its rank among the mask's set bits.
+constexpr int adj_mask_words(int N) { return 2 * ((N + 63) >> 6); }
+constexpr int adj_rank(const unsigned *mask, const unsigned *prefix, int i) {
+  return (int) prefix[i >> 5] + __builtin_popcount(mask[i >> 5] & ((1u << (i & 31)) - 1u));
+}
+// floats of the tables: a four-word header; per self contact the float4 normal (with its two slots) and the float4 d; per working-set slot
+// 1 / mass and the vertex; the layer offsets; per primitive-contact vertex nine planes (vertex, working-set slot or -1, n, d, mu)
+constexpr int adj_tables_floats(int nplist, int nself_verts, int nself, int nlayers) {
+  return round4(4 + 8 * nself + 2 * nself_verts + (nlayers + 1) + 9 * nplist);
+}
+// "fits": list (an entry per primitive-contact vertex and per working-set vertex), mask, counts and tables (with 3 floats for their 16-byte
+// alignment) inside the room, and the tables inside `tab_cap` floats (BwdArgs::ytab: 0 = no tables, the test hook caps them)
+constexpr bool adj_tables_fit(int ycap, int N, int nplist, int nself_verts, int nself, int nlayers, int tab_cap) {
+  const long long tab = adj_tables_floats(nplist, nself_verts, nself, nlayers);
+  return tab <= tab_cap && 3ll * (nplist + nself_verts) + 2ll * adj_mask_words(N) + tab + 3 <= 3ll * ycap;
+}
+
 // ---- split execution: K workgroups per rollout, R rows and HB boundary rows each side per part ----
 // forward (dc_forward_cl_kernel.h): [0, fric_floats) the gather arrays of the CG — with the single-exchange loop (`pipe`) the direction as
 // 8-byte rows and the neighbours' residual rows — or the element windows, which is also what the layered friction pass is offered; the

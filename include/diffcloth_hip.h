@@ -543,6 +543,12 @@ int dc_get_cluster_rows(const dc_ctx *ctx, int *rows_per_part, int *halo_rows);
  * layers itself (the parts share an XCD and the working set fits the LDS; DC_SELF_REDUNDANT=0 turns it off) instead of part 0 alone. All zero
  * when the batch runs one workgroup per rollout. Synchronises; reset != 0 zeroes the counters afterwards.                                    */
 int dc_get_self_friction_path(dc_ctx *ctx, int *out /*B*2*/, int reset);
+/* Which form the contact phase of the adjoint operator took, counted per rollout since dc_alloc_batch (or the last reset): out[2 b] = backward
+ * steps run by a kernel instance that can hold the step's contact tables in LDS (one workgroup per rollout, 1024 threads, diag(P)
+ * preconditioner), out[2 b + 1] = those of them whose tables fitted and were built: the CG applications of such a step take the contact phase
+ * from them (DC_ADJ_RESIDENT=0 turns them off; none are built for a step without self contacts on a mesh of fewer than 4 element windows,
+ * whose applications form y while staging). All zero for every other instance. Synchronises; reset != 0 zeroes the counters afterwards.   */
+int dc_get_adjoint_contact_path(dc_ctx *ctx, int *out /*B*2*/, int reset);
 /* Which kernel set dc_build chose for this system (works on a host-only context too): out6 = {vertices renumbered on the device
  * (0 / 1), bandwidth of the system matrix in device numbering, packet-matrix forward kernel usable (needs bandwidth <= 511),
  * LDS element windows usable, number of element windows, explicit-inverse solve (small meshes)}. A mesh that fails the packet /
