@@ -748,6 +748,13 @@ class Engine:
         self._chk(self.lib.dc_get_packet_layout(self.h, C.byref(k)))
         return bool(k.value)
 
+    def packet_layout(self):
+        """0 = column deltas (or no packet matrix), 1 = byte offsets, 2 = values only under a matrix-wide column-offset template
+        (dc_get_packet_layout; DC_PK_TPL=0 keeps the byte offsets)"""
+        k = C.c_int()
+        self._chk(self.lib.dc_get_packet_layout(self.h, C.byref(k)))
+        return int(k.value)
+
     def bend_rows(self):
         """True when dc_build turned the bending term into per-vertex matrix rows (dc_get_bend_rows; a mesh flat at rest, DC_BEND_ROWS=0 keeps the flaps)"""
         k = C.c_int()

@@ -75,6 +75,10 @@ struct DevSystem {
   int pk_vpt, pk_ok;            // rows per thread of the packet kernel; 0 = tables not usable (bandwidth > 511 or N too large)
   int pk_threads;               // threads of the packet kernel the tables are padded for (512 or 768)
   int pk_ofs;                   // pk is in the byte-offset layout of the instances that hold the direction as halves (dc_packets.h)
+  // pk_tpl: pk went on to the template layout (dc_packets.h: third layout) — per 64-row chunk three 16-byte slices of values, slot j the coefficient
+  // of column row + pk_tpl_off[j]; pk_guard = bytes of zero rows the kernel keeps on each side of the direction's 8-byte rows
+  int pk_tpl, pk_guard;
+  int pk_tpl_off[kPkTplSlots];
   int adj_coarse;               // the adjoint's fp64 fall-back adds the coarse correction over the deflation space (dc_adjoint64.h)
   const double DC_G *dsph_tri;  // discretised sphere (DC_PRIM_SPHERE_DISCRETIZED): [dsph_ntri][12] = p0, p1, p2, face normal of its mesh, creation order
   int dsph_ntri;
@@ -263,6 +267,7 @@ struct BwdArgs : BwdArgsStatic {
 // launching, when this build has no such instance; else the runtime's last error, peeked and not cleared (the engine clears it: launched()).
 hipError_t launch_pd_step(const DevSystem &S, const DevWork &W, const FwdArgs &A, const FwdChoice &ch, int B, hipStream_t st);
 hipError_t launch_pd_step_packet(const DevSystem &S, const DevWork &W, const FwdArgs &A, const FwdChoice &ch, int B, hipStream_t st);
+hipError_t launch_pd_step_packet_template(const DevSystem &S, const DevWork &W, const FwdArgs &A, const FwdChoice &ch, int B, hipStream_t st);
 hipError_t launch_pd_step_packet_deflated(const DevSystem &S, const DevWork &W, const FwdArgs &A, const FwdChoice &ch, int B, hipStream_t st);
 hipError_t launch_pd_step_resident(const DevSystem &S, const DevWork &W, const FwdArgs &A, const FwdChoice &ch, int B, hipStream_t st);
 void launch_self_detect(const DevSystem &S, const DevWork &W, const FwdArgs &A, int B, hipStream_t st);

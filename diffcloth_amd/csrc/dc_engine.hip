@@ -304,6 +304,8 @@ static void set_decisions(dc_ctx *c, const HostTables &plan) {
   c->fwd = forward_choice(c->facts, kernel_switches());
   S.win_ok = plan.win_ok; S.nwin = plan.nwin; S.pk_ok = plan.pk_ok; S.pk_vpt = plan.pk_vpt; S.pk_threads = plan.pk_threads;
   S.pk_ofs = plan.pk_ofs; S.win_rows = plan.bend_rows;
+  S.pk_tpl = plan.pk_tpl; S.pk_guard = plan.pk_guard_bytes;
+  for (int j = 0; j < kPkTplSlots; j++) S.pk_tpl_off[j] = plan.pk_tpl ? plan.pk.tpl_off[j] : 0;
   S.fwd_defl = plan.fwd_defl; S.adj_coarse = plan.adj_coarse; S.dense_ld = plan.dense_ld;
   S.max_radii = plan.max_radii; S.self_cap = plan.self_cap; S.self_lds = plan.self_lds;
 }
@@ -795,7 +797,8 @@ int dc_build(dc_ctx *c) {
   sw.pk_h16 = kernel_switches().pk_h16;                       // (read once per process with the other switches that select kernel instances)
   sw.pk_threads = env_int("DC_PK_THREADS", 0);                // 512 / 768 = threads of the packet kernel for meshes of 9 217 ... 10 240 vertices
   sw.pk_ofs = env_not_off("DC_PK_OFS", true);                 // 0 = the first packet layout (10-bit column deltas) for the halves instances too
-  sw.bend_rows = env_not_off("DC_BEND_ROWS", true);           // 0 = per-flap bending passes on meshes that are flat at rest too
+  sw.pk_tpl = env_not_off("DC_PK_TPL", true);                 // 0 = a matrix with a column-offset template keeps the byte-offset layout (values and offsets per row)
+  sw.bend_rows = env_not_off("DC_BEND_ROWS", true);          // 0 = per-flap bending passes on meshes that are flat at rest too
   HostTables plan;
   plan.build(H, p, sw);
   HostDeflation *HD = nullptr;
@@ -2228,7 +2231,7 @@ int dc_get_deflation(const dc_ctx *c, int *vectors, int *probe_iterations) {
 int dc_get_packet_layout(const dc_ctx *c, int *byte_offsets) {
   if (!c || !byte_offsets) return DC_ERR_INVALID;
   if (!c->built) return DC_ERR_STATE;
-  *byte_offsets = c->S.pk_ofs;
+  *byte_offsets = c->S.pk_tpl ? 2 : c->S.pk_ofs;
   return DC_OK;
 }
 

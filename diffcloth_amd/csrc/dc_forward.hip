@@ -185,7 +185,7 @@ __global__ __launch_bounds__(THREADS) void k_pd_step(const DevSystem *__restrict
 // resident, else this file's global-memory kernel, any N). No family is tried after another: a choice without an instance is an error.
 hipError_t launch_pd_step(const DevSystem &S, const DevWork &W, const FwdArgs &A, const FwdChoice &ch, int B, hipStream_t st) {
   switch (ch.family) {
-    case kFwdPacket: return launch_pd_step_packet(S, W, A, ch, B, st);
+    case kFwdPacket: return ch.tpl ? launch_pd_step_packet_template(S, W, A, ch, B, st) : launch_pd_step_packet(S, W, A, ch, B, st);
     case kFwdPacketDeflated: return launch_pd_step_packet_deflated(S, W, A, ch, B, st);
     case kFwdResident: return launch_pd_step_resident(S, W, A, ch, B, st);
     case kFwdGlobal: {

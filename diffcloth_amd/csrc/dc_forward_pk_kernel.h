@@ -36,19 +36,25 @@ namespace dc {
 // used, alpha = <d, r> / <d, A d>, and r, x are updated with that same d, so r stays the residual of x (fp32, as before) and the stopping
 // rule is unchanged; the rounding of d (2^-11 relative) costs a little conjugacy, nothing else. Needs the element windows (S.win_ok).
 // OFS (with H16): the packet matrix is in its byte-offset layout (dc_packets.h, S.pk_ofs) — one address instruction per non-zero of the product.
-template <int THREADS, int VPT, int XL, bool DETECT, bool DENSE, bool H16, bool DEFL, bool OFS>
+// TPL (with OFS, not DEFL): the matrix went on to its template layout (S.pk_tpl: values only, the column offsets are the same twelve for every row) —
+// no address instruction per non-zero, the row is the immediate offset of the gather (dc_pklib.h: PkTplRows). The direction's rows then lie
+// between two guards of S.pk_guard bytes of zeros, which the zero slots of the first and last rows point into.
+template <int THREADS, int VPT, int XL, bool DETECT, bool DENSE, bool H16, bool DEFL, bool OFS, bool TPL = false>
 __device__ __forceinline__ void pd_step_pk(const DevSystem *__restrict__ Sp, const DevWork &W, const FwdArgs &A) {
   static_assert(!(H16 && DENSE), "the explicit-inverse solve keeps the fp32 planes");
   static_assert(H16 || !OFS, "byte offsets address the direction's 8-byte rows");
+  static_assert(!TPL || (OFS && !DEFL), "the template layout follows from the byte offsets; deflate() writes floats into the direction's LDS, guards included");
   const DevSystem &S = *Sp;
   constexpr int NP = THREADS * VPT;
   constexpr int WAVES = THREADS / 64;
   constexpr int XR = VPT - XL;
   constexpr int PF = H16 ? 2 : 3;        // floats per row of the search direction in LDS
   extern __shared__ float lp[];          // search direction: float2 (x, y) [NP] then float z [NP] (H16: h4 [NP]); then x rows [XL][3][THREADS]
-  float *lx = lp + PF * NP;
-  h4 *lh = (h4 *) lp;
-  const unsigned lh_addr = lds_byte_address(lp);
+  int guard = 0;                         // TPL: bytes of each guard; the direction's rows start behind the lower one, lx behind the upper one
+  if constexpr (TPL) guard = Sp->pk_guard;
+  float *lx = lp + PF * NP + guard / 2;
+  h4 *lh = (h4 *) lp + guard / 8;
+  const unsigned lh_addr = lds_byte_address(lp) + (unsigned) guard;
   float *ldense = lp + 3 * THREADS * (VPT + XL);      // DENSE: partial sums of the product with the explicit inverse
   __shared__ double red[THREADS / 64];
   __shared__ double red2[H16 ? 2 * (THREADS / 64) : 1];
@@ -65,7 +71,8 @@ __device__ __forceinline__ void pd_step_pk(const DevSystem *__restrict__ Sp, con
   // H16 product: packet-row address and packet count of the wave's k-th chunk, held in lane k for the whole launch (see spmv)
   unsigned tbl_lo = 0, tbl_hi = 0;
   int tbl_n = 0;
-  if constexpr (H16) {
+  if constexpr (TPL) tbl_lo = 8u * (unsigned) S.pk_tpl_off[min(lane, kPkTplSlots - 1)];      // lane j = 8 x column offset of slot j (the chunks lie kPkTplBatchInt4 apart: no row table)
+  else if constexpr (H16) {
     const int ch = wv + min(lane, VPT - 1) * WAVES;
     const unsigned long long a = (unsigned long long) (S.pk + S.pk_ptr[ch]);
     tbl_lo = (unsigned) a; tbl_hi = (unsigned) (a >> 32); tbl_n = S.pk_n[ch];
@@ -412,11 +419,41 @@ __device__ __forceinline__ void pd_step_pk(const DevSystem *__restrict__ Sp, con
       pn = sqrtf((float) rz); hs = half_scale(pn);
 #pragma unroll
       for (int k = 0; k < VPT; k++) lh[tq + k * THREADS] = pack_h4(rr[k][0] * hs, rr[k][1] * hs, rr[k][2] * hs);
+      if constexpr (TPL) {                  // the guards: the windows, the friction layers and the detection have used this LDS since the last solve
+        const int gr = guard / 8;           // (2 gr <= THREADS: dc_tables.cpp)
+        if (tid < 2 * gr) lh[tid < gr ? tid - gr : NP + tid - gr] = pack_h4(0.f, 0.f, 0.f);
+      }
     }
     PH(1)
     // ap = Ahat * (the vector in lp), part2 += <lp, ap>; rows of a thread tid + k * THREADS
     auto spmv = [&](int wz, float &part2, bool with_pr, float &part3) {
-      if constexpr (H16) {
+      if constexpr (TPL) {
+        // (the opaque zero as in the branch below: the 13 bases and the chunk addresses are rebuilt per product, not hoisted out of the CG loop)
+        const int zl = wz - wv;
+        using Rows = PkTplRows<THREADS>;
+        const int4 DC_G *chunk = S.pk + (size_t) kPkTplBatchInt4 * (size_t) wz;
+        unsigned lane16 = 16u * (unsigned) lane;
+        asm("" : "+v"(lane16));
+        PkTplBatch nxt;
+        load_h_batch(nxt, chunk, lane16);
+        PkTplBases bases;
+        Rows::first(bases, lh_addr + 8u * (unsigned) (wz * 64 + lane), [&](int j) { return __builtin_amdgcn_readlane((int) tbl_lo, j + zl); });
+#pragma unroll
+        for (int j = 0; j < kPkTplSlots; j++) asm volatile("" : "+v"(bases.a[j]));      // opaque: one register per slot, not base + offset per gather
+        asm volatile("" : "+v"(bases.own));
+#pragma unroll
+        for (int k = 0; k < VPT; k++) {
+          const PkTplBatch cur = nxt;
+          if (k + 1 < VPT) load_h_batch(nxt, chunk + (size_t) kPkTplBatchInt4 * WAVES * (k + 1), lane16);
+          float ax, ay, az;
+          pk_v2i own;
+          Rows::consume(k, cur, bases, ax, ay, az, own);
+          ap[k][0] = ax; ap[k][1] = ay; ap[k][2] = az;
+          dot3_h(ax, ay, az, own, part2);
+          dot3_h(rr[k][0], rr[k][1], rr[k][2], own, part3);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      } else if constexpr (H16) {
         // Row table from the lanes (tbl_*: lane k = the wave's k-th chunk): one v_readlane per value instead of scalar loads of pk_ptr / pk_n
         // and of the table pointers themselves in every row — each of those was an `s_waitcnt lgkmcnt(0)`, i.e. an exposed scalar-cache
         // round trip that also drains the LDS gathers in flight (94 scalar loads per product in the round-4 code object). The lane
@@ -712,6 +749,36 @@ __global__ __launch_bounds__(THREADS) void k_pd_step_pk(const DevSystem *__restr
 template <int THREADS, int VPT, int XL, bool DETECT, bool DEFL>
 __global__ __launch_bounds__(THREADS) void k_pd_step_pk_d10(const DevSystem *__restrict__ Sp, DevWork W, FwdArgs A) {
   pd_step_pk<THREADS, VPT, XL, DETECT, false, true, DEFL, false>(Sp, W, A);
+}
+
+// k_pd_step_pk_tpl: the halves instance on the template layout (S.pk_tpl; dc_forward_pk_tpl.hip)
+template <int THREADS, int VPT, int XL, bool DETECT>
+__global__ __launch_bounds__(THREADS) void k_pd_step_pk_tpl(const DevSystem *__restrict__ Sp, DevWork W, FwdArgs A) {
+  pd_step_pk<THREADS, VPT, XL, DETECT, false, true, false, true, true>(Sp, W, A);
+}
+
+template <int THREADS, int VPT, int XL, bool DETECT>
+static void launch_pk_tpl_inst(const DevSystem &S, const DevWork &W, const FwdArgs &A, int B, hipStream_t st) {
+  const size_t lds = pk_lds_bytes(THREADS, VPT, XL, true, false, 0, S.win_ok, S.win_lds_bytes, A.inline_detect, S.pk_guard);
+  (void) ensure_dynamic_lds<k_pd_step_pk_tpl<THREADS, VPT, XL, DETECT>>(lds);      // (refused: the launch reports it)
+  hipLaunchKernelGGL((k_pd_step_pk_tpl<THREADS, VPT, XL, DETECT>), dim3(B), dim3(THREADS), lds, st, S.self_dev, W, A);
+}
+// the template-layout instance of the choice's shape: the shapes of kPkShapes that have a halves instance. hipErrorInvalidValue: the choice
+// or the tables name none. (A template so that only the translation unit that calls it instantiates the kernels.)
+template <int = 0>
+static hipError_t launch_pk_template_choice(const DevSystem &S, const DevWork &W, const FwdArgs &A, const FwdChoice &ch, int B, hipStream_t st) {
+  if (!ch.h16 || !ch.tpl || !S.pk_tpl) return hipErrorInvalidValue;
+  const bool hit = for_first_index<kPkShapeCount>([&](auto i) {
+    constexpr PkShape s = kPkShapes[i];
+    if constexpr (s.xl_h16 < 0) return false;
+    else {
+      if (ch.threads != s.threads || ch.vpt != s.vpt) return false;
+      if (A.inline_detect) launch_pk_tpl_inst<s.threads, s.vpt, s.xl_h16, true>(S, W, A, B, st);
+      else launch_pk_tpl_inst<s.threads, s.vpt, s.xl_h16, false>(S, W, A, B, st);
+      return true;
+    }
+  });
+  return hit ? hipPeekAtLastError() : hipErrorInvalidValue;
 }
 
 template <int THREADS, int VPT, int XL, bool DETECT, bool DENSE, bool H16 = false, bool DEFL = false>

@@ -17,7 +17,8 @@ namespace dc {
 // Forward, packet kernel (k_pd_step_pk, dc_forward_pk_kernel.h): threads x rows per thread; xl = rows of the iterate held in LDS with the fp32
 // direction planes, xl_h16 = with the direction as halves (-1: no such instance); dense = an instance with the explicit-inverse solve (rows <= 3);
 // defl = an instance with the deflated solve (512 threads, rows >= 4: dc_forward_pk_defl.hip). The halves instances read the packet matrix by
-// byte offsets, or by its 10-bit column deltas when the tables kept those (k_pd_step_pk_d10). min_n: a shape that is taken only when
+// byte offsets, by its 10-bit column deltas when the tables kept those (k_pd_step_pk_d10), or values only when the matrix has a column-offset
+// template (k_pd_step_pk_tpl). min_n: a shape that is taken only when
 // DC_PK_THREADS (or the default) names its thread count, and then from this many rows on; 0 = a shape of the default ladder. Order: the order
 // the launcher files instantiate in, which is the order the kernels stand in the code objects.
 struct PkShape { int threads, vpt, xl, xl_h16; bool dense, defl; int min_n; };
@@ -101,6 +102,7 @@ struct KernelSwitches {
 struct PlanFacts {
   int N = 0;
   bool pk_ok = false, win_ok = false, pk_ofs = false, fwd_defl = false, adj_coarse = false;
+  bool pk_tpl = false;                    // the packet matrix went on from byte offsets to the template layout (dc_packets.h)
   int pk_threads = 0, pk_vpt = 0;
   bool defl_space = false;                // a deflation space was built (DevSystem::defl_u)
   bool dense_inv = false;                 // the explicit inverse was built (DevSystem::dense_inv)
@@ -113,6 +115,7 @@ struct FwdChoice {
   FwdFamily family = kFwdNone;            // kFwdNone: the decisions name no compiled instance
   int threads = 0, vpt = 0, xl = 0;
   bool h16 = false, ofs = false, dense = false;   // packet families: direction as halves, matrix by byte offsets, explicit-inverse solve
+  bool tpl = false;                       // kFwdPacket with halves: the matrix is in its template layout, k_pd_step_pk_tpl runs (dc_forward_pk_tpl.hip)
   bool fusable = false;                   // the kernel honours FwdArgs::nsteps (all steps of a rollout in one launch): the packet families
 };
 // The packet kernel when its tables exist (deflated when the plan says so), else the ELL resident kernel up to its largest shape, else the
@@ -125,10 +128,10 @@ inline FwdChoice forward_choice(const PlanFacts &f, const KernelSwitches &sw) {
     for (const PkShape &s : kPkShapes) {
       if (s.threads != f.pk_threads || s.vpt != f.pk_vpt) continue;
       const bool h16 = sw.pk_h16 && f.win_ok && s.xl_h16 >= 0;      // the halves need the element windows
-      if ((defl && !s.defl) || (f.pk_ofs && !h16)) break;
+      if ((defl && !s.defl) || (f.pk_ofs && !h16) || (f.pk_tpl && (defl || !f.pk_ofs))) break;
       c.family = defl ? kFwdPacketDeflated : kFwdPacket;
       c.threads = s.threads; c.vpt = s.vpt; c.xl = h16 ? s.xl_h16 : s.xl;
-      c.h16 = h16; c.ofs = f.pk_ofs; c.dense = !defl && s.dense && f.dense_inv;
+      c.h16 = h16; c.ofs = f.pk_ofs; c.tpl = f.pk_tpl; c.dense = !defl && s.dense && f.dense_inv;
       c.fusable = true;
       break;
     }

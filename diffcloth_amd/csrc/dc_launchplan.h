@@ -22,6 +22,11 @@ constexpr long long kSpinLimit = 200000000ll;     // bound of every spin of the 
 constexpr int kSelfCells = 4096;               // bins of the 2-D broad-phase grid of the self-contact detection
 constexpr int kSelfDetectLdsInts = 16 + (kSelfCells + 1) + kSelfCells + 1 + 2048;   // LDS ints self_detect_rollout needs
 constexpr int kPkOfsBatchInt4 = 4 * 64 + 32;   // 16-byte units of a 64-row chunk's batch (12 non-zeros per row) in the packet matrix's byte-offset layout (dc_packets.h)
+constexpr int kPkTplSlots = 12;                // column offsets of the packet matrix's template layout (dc_packets.h): one batch per row
+constexpr int kPkTplBatchInt4 = 3 * 64;        // 16-byte units of a 64-row chunk in that layout: 12 values per row, nothing else
+// bytes of zero rows the template layout keeps on each side of the direction's 8-byte rows: a slot of a boundary row may point max_abs_off rows
+// before row 0 or behind the last row
+constexpr int pk_tpl_guard_bytes(int max_abs_off) { return (8 * max_abs_off + 15) / 16 * 16; }
 constexpr int kCoarseVectors = 16;
 constexpr int kCoarseLdsFloats = 2 * (16 * 3 * kCoarseVectors + 3 * kCoarseVectors);      // scratch of precondition64 in floats (16 = waves or parts, at most)
 // explicit inverse of small systems (dc_denselib.h): number of column chunks the product is split into so that every wave of the workgroup
@@ -37,9 +42,10 @@ constexpr int round4(int floats) { return (floats + 3) / 4 * 4; }
 
 // ---- one workgroup per rollout ----
 // forward, packet kernel (dc_forward_pk_kernel.h): direction (8-byte rows with H16) + XL rows of the iterate per thread, the explicit inverse's
-// partial sums behind them; the element windows and the inlined detection reuse the same bytes
-inline size_t pk_lds_bytes(int threads, int vpt, int xl, bool h16, bool dense, int dense_ld, bool win_ok, int win_lds_bytes, bool inline_detect) {
-  size_t lds = (size_t) threads * ((h16 ? 2 : 3) * vpt + 3 * xl) * sizeof(float);
+// partial sums behind them; the element windows and the inlined detection reuse the same bytes. guard_bytes: the zero rows on each side of the
+// direction when the packet matrix is in its template layout (pk_tpl_guard_bytes), 0 otherwise
+inline size_t pk_lds_bytes(int threads, int vpt, int xl, bool h16, bool dense, int dense_ld, bool win_ok, int win_lds_bytes, bool inline_detect, int guard_bytes = 0) {
+  size_t lds = (size_t) threads * ((h16 ? 2 : 3) * vpt + 3 * xl) * sizeof(float) + 2 * (size_t) guard_bytes;
   if (dense) lds += sizeof(float) * (size_t) dense_lds_floats(dense_ld, threads / 64);
   if (win_ok) lds = std::max(lds, (size_t) win_lds_bytes);
   if (inline_detect) lds = std::max(lds, sizeof(int) * (size_t) kSelfDetectLdsInts);

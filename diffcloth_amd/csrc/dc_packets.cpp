@@ -98,4 +98,54 @@ void HostPackets::to_offsets() {
   ofs = true;
 }
 
+bool HostPackets::to_template() {
+  if (!ok || !ofs || tpl) return false;
+  const size_t nch = pk_ptr.size();
+  for (size_t ch = 0; ch < nch; ch++) if (pk_n[ch] != 4) return false;      // a row of more than one batch
+  // entry n of row (ch, l): value bits and column - row; the padding entries sit on the row itself (offset 0, value 0)
+  auto entry = [&](size_t ch, int l, int n, int &bits) {
+    const int *b = &pk[4 * (size_t) pk_ptr[ch]];
+    bits = b[4 * (32 + 64 * (n / 4) + l) + n % 4];
+    const unsigned w = (unsigned) (n < 8 ? b[4 * (32 + 64 * 3 + l) + n / 2] : b[2 * l + (n - 8) / 2]);
+    return (int) (((n & 1) ? w >> 16 : w & 0xffffu) / 8u) - 512;
+  };
+  std::vector<int> offs;
+  for (size_t ch = 0; ch < nch; ch++)
+    for (int l = 0; l < 64; l++) {
+      int last = -1024;
+      for (int n = 0; n < 12; n++) {
+        int bits;
+        const int d = entry(ch, l, n, bits);
+        if (d == 0) continue;
+        if (d <= last) return false;      // the slots keep the row's order only when that order is ascending
+        last = d;
+        if (std::find(offs.begin(), offs.end(), d) == offs.end()) {
+          if ((int) offs.size() == kPkTplSlots) return false;
+          offs.push_back(d);
+        }
+      }
+    }
+  std::sort(offs.begin(), offs.end());
+  std::vector<int> out((size_t) 4 * kPkTplBatchInt4 * nch, 0), ptr(nch, 0);
+  for (size_t ch = 0; ch < nch; ch++) {
+    ptr[ch] = (int) (kPkTplBatchInt4 * ch);
+    for (int l = 0; l < 64; l++)
+      for (int n = 0; n < 12; n++) {
+        int bits;
+        const int d = entry(ch, l, n, bits);
+        if (d == 0) continue;
+        const int j = (int) (std::lower_bound(offs.begin(), offs.end(), d) - offs.begin());
+        out[4 * ((size_t) ptr[ch] + 64 * (j / 4) + l) + j % 4] = bits;
+      }
+  }
+  tpl_reach = 0;
+  for (int j = 0; j < kPkTplSlots; j++) {
+    tpl_off[j] = j < (int) offs.size() ? offs[j] : 0;
+    tpl_reach = std::max(tpl_reach, std::abs(tpl_off[j]));
+  }
+  pk.swap(out); pk_ptr.swap(ptr);
+  tpl = true;
+  return true;
+}
+
 }  // namespace dc

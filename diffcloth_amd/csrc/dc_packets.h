@@ -13,6 +13,14 @@
 // batch t of chunk c starts at pk[4 * (pk_ptr[c] + kPkOfsBatchInt4 * t)], the 8-byte slice at + 2 * lane, 16-byte slice j at
 // + 4 * (32 + 64 j + lane). 6 B per non-zero instead of 5.33. pk_n stays the packet count of the first layout (4 per batch), pk_ptr stays in
 // 16-byte units. Padding entries are value 0, offset 8 * 512 (the row itself).
+//
+// Third layout (to_template, from the second): values only. On a mesh whose numbering is regular — a row-major grid — the off-diagonals of
+// every row stand at the same few columns relative to the row: when the whole matrix has at most kPkTplSlots = 12 distinct offsets
+// (column - row) and no row needs a second batch, the offsets are a property of the matrix, not of the row. The template holds them in
+// ascending order (padded with 0, the row itself), a row is 12 fp32 values, slot j the coefficient of column row + tpl_off[j], and a slot
+// whose neighbour the row lacks holds 0: the same non-zeros in the same order, exact zeros interleaved. Chunk c is three 16-byte slices
+// {v0 .. v3}, {v4 .. v7}, {v8 .. v11} at pk[4 * (kPkTplBatchInt4 * c + 64 j + lane)]: 48 B per row instead of 72. A zero slot of a boundary
+// row may point up to tpl_reach rows outside the matrix: the kernel keeps that many zero rows on each side of the direction (dc_launchplan.h).
 #pragma once
 #include <vector>
 #include "dc_kernelplan.h"
@@ -23,6 +31,9 @@ namespace dc {
 struct HostPackets {
   bool ok = false;
   bool ofs = false;               // pk is in the second layout (byte-offset fields)
+  bool tpl = false;               // pk is in the third layout (values only; implies ofs: not the first layout)
+  int tpl_off[kPkTplSlots] = {};  // third layout: column - row of slot j, ascending; unused slots 0
+  int tpl_reach = 0;              // third layout: max |tpl_off|
   int vpt = 0;                    // rows per thread of the kernel the tables are padded for (threads * vpt rows)
   int threads = 512;              // threads of that kernel: 512, or 768 for the largest meshes (3 waves per SIMD, dc_forward_pk.hip)
   int shape = -1;                 // that kernel's entry of kPkShapes (dc_kernelplan.h); -1 = padded by build_rows for another kernel
@@ -37,6 +48,9 @@ struct HostPackets {
   bool build_rows(const HostSystem &H, int rows_padded);
   // rewrites pk / pk_ptr from the first layout into the second (pk_n, sq_dinv unchanged)
   void to_offsets();
+  // rewrites pk / pk_ptr from the second layout into the third; false (and nothing changed) when the matrix has more than kPkTplSlots distinct
+  // offsets, a row of more than one batch, or a row whose entries are not in ascending column order
+  bool to_template();
 };
 
 }  // namespace dc

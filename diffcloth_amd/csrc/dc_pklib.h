@@ -213,6 +213,63 @@ __device__ __forceinline__ void consume_h_row(const PkOfsBatch &e, unsigned rowb
   asm("v_fma_mix_f32 %0, 1.0, %1, %0 op_sel_hi:[0,1,0]" : "+v"(az) : "v"(o.y));
   own = o;
 }
+// The row consumer of the packet matrix's template layout (dc_packets.h: third layout): a batch is 12 values, slot j the coefficient of the
+// column `row + offset j` with the 12 offsets the same for every row of the matrix. A thread's rows lie ROWSTRIDE rows apart, so slot j of its
+// k-th row is at A_j + 8 ROWSTRIDE k with A_j = (LDS address of the first row's entry) + 8 offset j: the 12 addresses A_j and the own entry's
+// are formed once per product (PkTplBases) and the row enters as the immediate offset of the gather — 4 wave-instructions per non-zero
+// (ds_read_b64, three v_fma_mix_f32) and 48 B of stream per row. The immediate has 16 bits: after kRefresh rows the bases move on by as many.
+// Same gathers, same products in the same order as consume_h_row: a slot whose neighbour the row lacks multiplies 0 with a finite half (a
+// neighbouring row's entry, or a zero guard row outside the matrix), which leaves the sums as they are.
+struct PkTplBatch { int4 v[3]; };
+// `chunk`: the chunk's three slices (wave-uniform), lane16 = 16 * lane as an unsigned register of its own: scalar base + 32-bit lane offset +
+// immediate (from `chunk[64 j + lane]` the compiler forms 64-bit vector addresses, four VALU instructions per row)
+__device__ __forceinline__ void load_h_batch(PkTplBatch &e, const int4 DC_G *chunk, unsigned lane16) {
+  const char DC_G *b = (const char DC_G *) chunk;
+#pragma unroll
+  for (int j = 0; j < 3; j++) e.v[j] = *(const int4 DC_G *) (b + lane16 + 1024 * j);
+}
+struct PkTplBases { unsigned a[kPkTplSlots], own; };
+template <int ROWSTRIDE>
+struct PkTplRows {
+  static constexpr int kRefresh = 65535 / (8 * ROWSTRIDE) + 1;      // rows a set of bases reaches: 16 at 512 threads, 11 at 768
+  // bases of the thread's first row; own0 = LDS byte address of that row's own entry, ofs8(j) = 8 * offset j
+  template <class F>
+  static __device__ __forceinline__ void first(PkTplBases &B, unsigned own0, F &&ofs8) {
+    B.own = own0;
+#pragma unroll
+    for (int j = 0; j < kPkTplSlots; j++) B.a[j] = own0 + (unsigned) ofs8(j);
+  }
+  // row k of the thread (the index of a fully unrolled loop: a constant where it is used)
+  static __device__ __forceinline__ void consume(int k, const PkTplBatch &e, PkTplBases &B, float &ax, float &ay, float &az, pk_v2i &own) {
+    if (k > 0 && k % kRefresh == 0) {
+#pragma unroll
+      for (int j = 0; j < kPkTplSlots; j++) B.a[j] += 8u * ROWSTRIDE * kRefresh;
+      B.own += 8u * ROWSTRIDE * kRefresh;
+    }
+    const int R = (k % kRefresh) * ROWSTRIDE;      // in rows of 8 bytes: the gather's immediate offset
+    pk_v2i q[12];
+#pragma unroll
+    for (int j = 0; j < kPkTplSlots; j++) q[j] = ((lds_int2p) (size_t) B.a[j])[R];
+    const pk_v2i o = ((lds_int2p) (size_t) B.own)[R];
+    __builtin_amdgcn_sched_barrier(0);      // (see consume_h)
+    ax = 0.f; ay = 0.f; az = 0.f;
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      fma3_h(__int_as_float(e.v[j].x), q[4 * j].x, q[4 * j].y, ax, ay, az);
+      fma3_h(__int_as_float(e.v[j].y), q[4 * j + 1].x, q[4 * j + 1].y, ax, ay, az);
+      fma3_h(__int_as_float(e.v[j].z), q[4 * j + 2].x, q[4 * j + 2].y, ax, ay, az);
+      fma3_h(__int_as_float(e.v[j].w), q[4 * j + 3].x, q[4 * j + 3].y, ax, ay, az);
+    }
+    asm("v_fma_mix_f32 %0, 1.0, %1, %0 op_sel_hi:[0,1,0]" : "+v"(ax) : "v"(o.x));
+    asm("v_fma_mix_f32 %0, 1.0, %1, %0 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "+v"(ay) : "v"(o.x));
+    asm("v_fma_mix_f32 %0, 1.0, %1, %0 op_sel_hi:[0,1,0]" : "+v"(az) : "v"(o.y));
+    // the caller's dot products with the own entry stay behind the sums: scheduled ahead, the first of them waits for ALL gathers of the row
+    // (the own entry is the last read) before the third product has issued
+    int ox = o.x, oy = o.y;
+    asm("" : "+v"(ox), "+v"(oy) : "v"(ax), "v"(ay), "v"(az));
+    own.x = ox; own.y = oy;
+  }
+};
 // acc += <(x, y, z), the three halves of q>: the dot products of the product loop take the direction's halves as they are, behind the sums
 __device__ __forceinline__ void dot3_h(float x, float y, float z, pk_v2i q, float &acc) {
   asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel_hi:[0,1,0]" : "+v"(acc) : "v"(x), "v"(q.x));

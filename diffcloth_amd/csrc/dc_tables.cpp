@@ -91,12 +91,28 @@ void HostTables::set_deflation(bool built, const TableSwitches &sw) {
   fwd_defl = (built && (!pk_ok || kPkShapes[pk.shape].defl)) ? 1 : 0;
   defl_built = built;
   adj_coarse = (built && sw.adj_coarse) ? 1 : 0;
+  // The template layout (dc_packets.h) for the plain halves instance: the deflated instances use the direction's LDS as float scratch and keep
+  // the byte offsets. The guards must fit the CU's LDS next to everything pk_lds_bytes counts (with the inlined detection, the larger request)
+  // and the kernel's static LDS, and the kernel zeroes them with one 8-byte store per thread.
+  if (sw.pk_tpl && pk_ofs && !pk_tpl && !fwd_defl) {
+    HostPackets t = pk;
+    if (t.to_template()) {
+      const PkShape &s = kPkShapes[pk.shape];
+      const int guard = pk_tpl_guard_bytes(t.tpl_reach);
+      const size_t lds = pk_lds_bytes(s.threads, s.vpt, s.xl_h16, true, false, 0, win_ok != 0, (int) win.lds_bytes, true, guard);
+      const size_t static_lds = sizeof(double) * 3 * (size_t) (s.threads / 64);      // the kernel's reduction scratch: red, red2
+      if (lds + std::max(static_lds, (size_t) kLdsReserveBytes) <= (size_t) kLdsLimitBytes && 2 * (guard / 8) <= s.threads) {
+        pk = std::move(t);
+        pk_tpl = 1; pk_guard_bytes = guard;
+      }
+    }
+  }
 }
 
 PlanFacts HostTables::facts(int N) const {
   PlanFacts f;
   f.N = N;
-  f.pk_ok = pk_ok != 0; f.pk_threads = pk_threads; f.pk_vpt = pk_vpt; f.win_ok = win_ok != 0; f.pk_ofs = pk_ofs != 0;
+  f.pk_ok = pk_ok != 0; f.pk_threads = pk_threads; f.pk_vpt = pk_vpt; f.win_ok = win_ok != 0; f.pk_ofs = pk_ofs != 0; f.pk_tpl = pk_tpl != 0;
   f.fwd_defl = fwd_defl != 0; f.adj_coarse = adj_coarse != 0; f.defl_space = defl_built; f.dense_inv = dense_ld != 0;
   f.win_lds_bytes = win_ok ? (int) win.lds_bytes : 0;
   return f;

@@ -26,6 +26,7 @@ struct TableSwitches {
   bool adj_coarse = true;   // DC_ADJ_COARSE=0: no coarse level over the deflation space in the adjoint's fall-back
   bool pk_h16 = true;       // DC_PK_H16=0: the packet kernels' 20- and 14-rows-per-thread instances keep the fp32 direction planes
   bool pk_ofs = true;       // DC_PK_OFS=0: the instances with the direction as halves read the packet matrix in its first layout
+  bool pk_tpl = true;       // DC_PK_TPL=0: a matrix with a column-offset template keeps the byte-offset layout too
   int pk_threads = 0;       // DC_PK_THREADS: 512 / 768 = threads of the packet kernel where both shapes exist (0: the default, dc_kernelplan.h)
   bool bend_rows = true;    // DC_BEND_ROWS=0: a mesh whose flaps are all flat at rest keeps the per-flap passes too (dc_windows.h: rows)
 };
@@ -37,6 +38,7 @@ struct HostTables {
   int pk_ok = 0, pk_vpt = 0, pk_threads = 0;   // packet matrix (pk): rows per thread and threads of its kernel, 0 when the tables are refused
   int bend_rows = 0;                   // the windows of the one-workgroup kernels carry the bending term as matrix rows, no flaps (win.rows)
   int pk_ofs = 0;                      // pk is in the byte-offset layout (dc_packets.h): the kernel that runs holds the direction as halves
+  int pk_tpl = 0, pk_guard_bytes = 0;  // set_deflation: pk went on to the template layout (values only, dc_packets.h); the zero rows each side of the direction
   int defl_rows = 0;                   // row padding of the deflation tables: the packet kernel's rows, or N rounded up to 64; 0 = no space wanted
   int fwd_defl = 0, adj_coarse = 0;    // set_deflation
   bool defl_built = false;             // set_deflation: the context has a deflation space
@@ -59,7 +61,9 @@ struct HostTables {
   HostDense dense;
 
   void build(const HostSystem &H, const dc_params &p, const TableSwitches &sw);
-  // `built`: the context has a deflation space for defl_rows rows
+  // `built`: the context has a deflation space for defl_rows rows. Also the last layout decision, which needs this one: the packet matrix
+  // goes from byte offsets to the template layout when it has a template, the plain (not deflated) halves instance runs, and the guard rows
+  // fit the LDS and one store per thread; otherwise it stays in the byte-offset layout, byte for byte
   void set_deflation(bool built, const TableSwitches &sw);
   // the decisions as the kernel choices of dc_kernelplan.h take them (after set_deflation)
   PlanFacts facts(int N) const;

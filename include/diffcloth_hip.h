@@ -555,7 +555,8 @@ int dc_get_adjoint_contact_path(dc_ctx *ctx, int *out /*B*2*/, int reset);
  * window conditions runs on the global-memory fallback kernels — correct, but several times slower. */
 int dc_get_layout(const dc_ctx *ctx, int *out6);
 /* Layout of the packet matrix dc_build chose (works on a host-only context): 1 = 16-bit byte offsets (the forward kernel instances that hold
- * the search direction as halves), 0 = 10-bit column deltas or no packet matrix. DC_PK_OFS=0 at dc_build keeps the column deltas.   */
+ * the search direction as halves), 0 = 10-bit column deltas or no packet matrix, 2 = values only under a matrix-wide template of at most 12
+ * column offsets (regularly numbered meshes: a row-major grid). DC_PK_OFS=0 at dc_build keeps the column deltas, DC_PK_TPL=0 the byte offsets. */
 int dc_get_packet_layout(const dc_ctx *ctx, int *byte_offsets);
 /* Whether dc_build turned the bending term of the one-workgroup kernels into per-vertex matrix rows (works on a host-only context): 1 = every
  * flap of the mesh is flat at rest (fp32 rest norm <= 1e-6) and the element windows carry no flaps, 0 = per-flap passes (any curved flap, no

@@ -28,7 +28,8 @@ FIELDS = ("vgpr_count", "agpr_count", "vgpr_spill_count", "sgpr_count", "sgpr_sp
 
 # The instances the headline (bench.py: 256 x 1 and 32 x 8) and the BASELINE configurations launch, by demangled-name prefix.
 HOT = {
-    "bench forward 256x1": "dc::k_pd_step_pk<512, 20, 12, true, false, true, false>",
+    "bench forward 256x1": "dc::k_pd_step_pk_tpl<512, 20, 12, true>",      # (the packet matrix's template layout; DC_PK_TPL=0: the next entry)
+    "bench forward 256x1, byte offsets": "dc::k_pd_step_pk<512, 20, 12, true, false, true, false>",
     "bench adjoint 256x1": "dc::k_adjoint_step<1024, true, false, false, false>",
     "bench forward 32x8": "dc::k_pd_step_cl<512, 3, true, true, false>",      # (PIPE = true: the single-exchange CG, round 6)
     "bench adjoint 32x8": "dc::k_adjoint_step_cl<512, false, false>",
