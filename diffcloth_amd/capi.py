@@ -74,6 +74,7 @@ EXPORTED_SYMBOLS = [
     "dc_set_primitive_shapes", "dc_set_primitive_shape_schedule", "dc_set_primitive_shapes_dev", "dc_set_primitive_shape_schedule_dev",
     "dc_get_primitive_shapes",
     "dc_get_contact_readout", "dc_get_contact_readout_dev",
+    "dc_set_contact_readout_gradients", "dc_set_contact_readout_gradients_dev",
 ]
 
 _lib = None
@@ -448,6 +449,37 @@ class Engine:
             ps = C.c_void_p(state.data_ptr())
         (pj, pw), f = self._tps((normal_impulse, self.B * self.N, nslots), (wrench, self.B * self.ngroups * 10, nslots))
         self._chk(self.lib.dc_get_contact_readout_dev(self.h, C.c_int(slot0), C.c_int(nslots), ps, pj, pw, C.c_int(f)))
+
+    def set_contact_readout_gradients(self, slot0=1, dL_djn=None, dL_dwrench=None):
+        """dc_set_contact_readout_gradients: the gradient of a loss with respect to the contact read-out of the records slot0 .. slot0 + nslots - 1,
+        dL_djn [nslots][B][N] and / or dL_dwrench [nslots][B][G][10] (entries 7..9, the counts, are ignored); nslots is the arrays' leading
+        dimension. The backward steps and sweeps through those records then add the read-out's part to every gradient they leave. One of the
+        two may be None (zeros); both None clears all weights, as clear_schedules and alloc_batch do."""
+        j, w = _f64(dL_djn), _f64(dL_dwrench)
+        if j is None and w is None:
+            self._chk(self.lib.dc_set_contact_readout_gradients(self.h, C.c_int(int(slot0)), C.c_int(0), None, None))
+            return
+        nslots = None
+        if j is not None:
+            j = j.reshape(-1, self.B, self.N)
+            nslots = j.shape[0]
+        if w is not None:
+            w = w.reshape(-1, self.B, self.ngroups, 10)
+            if nslots is not None and w.shape[0] != nslots:
+                raise ValueError(f"set_contact_readout_gradients: dL_djn covers {nslots} slot(s), dL_dwrench {w.shape[0]}")
+            nslots = w.shape[0]
+        slot0, nslots = self._readout_range(slot0, nslots)
+        self._chk(self.lib.dc_set_contact_readout_gradients(self.h, C.c_int(slot0), C.c_int(nslots), _d(j), _d(w)))
+
+    def set_contact_readout_gradients_dev(self, slot0, nslots, dL_djn=None, dL_dwrench=None):
+        """dc_set_contact_readout_gradients_dev from CUDA tensors of one floating dtype: dL_djn [nslots][B][N], dL_dwrench [nslots][B][G][10];
+        one may be None (zeros), both None clears all weights. Only enqueued on the context's stream."""
+        if dL_djn is None and dL_dwrench is None:
+            self._chk(self.lib.dc_set_contact_readout_gradients_dev(self.h, C.c_int(int(slot0)), C.c_int(0), None, None, C.c_int(1)))
+            return
+        slot0, nslots = self._readout_range(slot0, nslots)
+        (pj, pw), f = self._tps((dL_djn, self.B * self.N, nslots), (dL_dwrench, self.B * self.ngroups * 10, nslots))
+        self._chk(self.lib.dc_set_contact_readout_gradients_dev(self.h, C.c_int(slot0), C.c_int(nslots), pj, pw, C.c_int(f)))
 
     def get_self_contacts(self, slot, rollout=0, cap=8192):
         cnt = C.c_int(); nl = C.c_int()

@@ -70,6 +70,16 @@ struct dc_ctx {
   float *FVS_S = nullptr;           // [(tape+1)][B] factor on fv of that step
   float *SEEDX = nullptr, *SEEDV = nullptr;   // [(tape+1)][B][3][N] loss gradient w.r.t. the state at the slot (allocated on first use)
   std::vector<char> sched_xf, sched_fu, sched_fvs, sched_seed;
+  // gradients of a loss on the contact read-out (dc_set_contact_readout_gradients), allocated by the first setter after dc_alloc_batch: the
+  // weights per record in device numbering, a device flag per slot, and the seed rows the backward sweep reads in place of the caller's schedule
+  // while a record of the sweep carries weights (caller's entry + the read-out's part; the caller's schedule is never written)
+  float *RWJ = nullptr;             // [(tape+1)][B][N] dL/djn
+  float *RWW = nullptr;             // [(tape+1)][B][G][10] dL/dwrench
+  unsigned char *rw_has = nullptr;  // [(tape+1)] 1 = the slot carries weights
+  float *RSX = nullptr, *RSV = nullptr;       // [(tape+1)][B][3][N]
+  std::vector<char> sched_rw;
+  int rw_arrived = -1;              // the state the last backward call arrived at when the gradient it left holds the read-out's part of that record; -1 = none
+  int rw_launches = 0;              // launches of the read-out's adjoint passes in the sweep being enqueued (dc_kernel_times counts them)
   // movable obstacles (dc_set_primitive_offsets / dc_set_primitive_offset_schedule, dc_primoffset.h): absolute fp32 centres of the P flattened
   // primitives. Every row of PC is valid at all times — the built centres until something else is written — and the forward kernels always
   // read the row of the slot their step produces, so a slot says where its obstacle was (dc_get_primitive_centers).

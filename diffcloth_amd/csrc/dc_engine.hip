@@ -12,6 +12,7 @@
 #include "dc_env.h"
 #include "dc_primoffset.h"
 #include "dc_primshape.h"
+#include "dc_readout_adjoint.h"
 #include "dc_record.h"
 #include "dc_tables.h"
 #include "dc_spheremesh.h"
@@ -486,6 +487,7 @@ static int launched(dc_ctx *c, hipError_t e, const char *step, int threads, int 
 }
 
 int enqueue_pd_step(dc_ctx *c, const FwdArgs &A) {
+  c->rw_arrived = -1;      // records are being rewritten: no backward chain continues across a forward step
   {   // a forward step overwrites records: a record handed in from outside for one of them (dc_set_record) is gone
     const long first = (long) ((A.x_out - c->X) / (long) slot_elems(c));
     if (c->inj_slot >= first && c->inj_slot < first + A.nsteps) c->inj_slot = -1;
@@ -582,6 +584,25 @@ int enqueue_forward_steps(dc_ctx *c, int slot, int nsteps, bool carry_targets, i
   return DC_OK;
 }
 
+// drops the read-out weights (both pointers NULL, dc_clear_schedules): enqueued, the tables keep their memory
+int clear_readout_gradients(dc_ctx *c) {
+  std::fill(c->sched_rw.begin(), c->sched_rw.end(), 0);
+  c->rw_arrived = -1;
+  if (c->rw_has) HIPCHK(c, hipMemsetAsync(c->rw_has, 0, (size_t) c->tape + 1, c->stream));
+  return DC_OK;
+}
+ReadoutAdjArgs readout_adjoint_args(dc_ctx *c, int slot, int first) {
+  ReadoutAdjArgs A;
+  A.X = c->X; A.V = c->V; A.F = c->F; A.NRM = c->NRM; A.PRIM = c->PRIM; A.PC = c->PC; A.PV = c->PV; A.XF = c->XF; A.mu = c->mu;
+  A.WJ = c->RWJ; A.WW = c->RWW; A.has = c->rw_has;
+  A.B = c->B; A.slot = slot; A.first = first;
+  const bool inj = c->inj_slot >= first - 1 && c->inj_slot <= slot && c->INJ_X;
+  A.inj_x = inj ? c->INJ_X : nullptr; A.inj_f = inj ? c->INJ_F : nullptr; A.inj_n = inj ? c->INJ_N : nullptr; A.inj_slot = inj ? c->inj_slot : -1;
+  A.gx = c->GX; A.rsx = c->RSX; A.rsv = c->RSV;
+  A.DPAR = c->DPAR; A.DXF = c->DXF; A.YS = (c->keep_y && c->YS) ? c->YS : nullptr; A.DMU = c->DMU; A.DPV = c->PV ? c->DPV : nullptr;
+  return A;
+}
+
 // The backward steps through the records slot, slot - 1 ... slot - nsteps + 1, enqueued on the context's stream: dL_dxfixed of those slots is
 // zeroed (the kernels add to it; DMU is the caller's: the per-step calls zero it, a sweep accumulates into what dc_seed_gradient / dc_set_gradient
 // zeroed), then one launch per step or, fused, the whole sweep of a rollout in ONE launch. A record handed in from outside (dc_set_record) gets
@@ -601,13 +622,57 @@ int enqueue_backward_steps(dc_ctx *c, int slot, int nsteps, Seeds seeds, const b
   const bool inj_inside = c->inj_slot >= first && c->inj_slot <= slot;
   const bool fused = fuse_steps_enabled() && nsteps > 1 && !inj_inside && c->params.adjoint_mode != 2 && c->params.adjoint_mode != 3;
   auto start_of = [&](int s) { return is_start ? *is_start : s == c->start_slot + 1; };
+  // A record of the sweep carries read-out weights (dc_set_contact_readout_gradients): the seed pass adds the read-out's part of the loss gradient
+  // to the engine's own seed rows of the states slot - 1 .. first - 1, which start as the caller's entries (schedule, init gradients or zeros) and
+  // which every step of this sweep then reads in their place; the parameter pass follows the steps. The gradient a call leaves is that of the
+  // state it ARRIVES at, first - 1, and holds the read-out's part of record first - 1 (its row is a seed row like the others): a call that starts
+  // where the last one arrived (a chain of per-step calls or of sweeps) finds it in the carried gradient, every other call adds the part of its
+  // top record to the carried gradient itself. Either way the part is added to the caller's entry first and enters the step's fp64 sum as one
+  // fp32 vector: a fused sweep and a chain of per-step calls over the same tape give the same bits.
+  bool rw = false;
+  if (c->RSV) for (int s = std::max(first - 1, 1); s <= slot; s++) rw = rw || c->sched_rw[s];
+  const bool top_done = rw && c->rw_arrived == slot;
+  c->rw_arrived = (rw && first - 1 >= 1 && c->sched_rw[first - 1]) ? first - 1 : -1;
+  c->rw_launches = 0;
+  const size_t se = slot_elems(c);
+  ReadoutAdjArgs RA;
+  if (rw) {
+    float *bx = c->RSX + se * (first - 1), *bv = c->RSV + se * (first - 1);
+    const size_t bytes = sizeof(float) * se * nsteps;
+    if (seeds == Seeds::schedule && c->SEEDX && c->sched_seed[slot - 1]) {
+      HIPCHK(c, hipMemcpyAsync(bx, seedx_slot(c, first - 1), bytes, hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(bv, seedv_slot(c, first - 1), bytes, hipMemcpyDeviceToDevice, c->stream));
+    } else if (seeds == Seeds::init) {
+      for (int k = 0; k < nsteps; k++) {
+        HIPCHK(c, hipMemcpyAsync(bx + se * k, c->IX, sizeof(float) * se, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(bv + se * k, c->IV, sizeof(float) * se, hipMemcpyDeviceToDevice, c->stream));
+      }
+    } else {
+      HIPCHK(c, hipMemsetAsync(bx, 0, bytes, c->stream));
+      HIPCHK(c, hipMemsetAsync(bv, 0, bytes, c->stream));
+    }
+    RA = readout_adjoint_args(c, slot, first);
+    RA.top_done = top_done ? 1 : 0;
+    launch_readout_adjoint(c->S, c->W, RA, 0, c->stream);
+    HIPCHK(c, hipGetLastError());
+  }
+  auto args_of = [&](int s) {
+    BwdArgs A = bwd_args(c, s, start_of(s), seeds);
+    if (rw) { A.ix = c->RSX + se * (s - 1); A.iv = c->RSV + se * (s - 1); A.slot_ix = se; }
+    return A;
+  };
   if (fused) {
-    BwdArgs A = bwd_args(c, slot, start_of(slot), seeds);
+    BwdArgs A = args_of(slot);
     A.nsteps = nsteps;
     if ((rc = enqueue_adjoint_step(c, A))) return rc;
   } else {
     for (int s = slot; s >= first; s--)
-      if ((rc = enqueue_adjoint_step(c, bwd_args(c, s, start_of(s), seeds)))) return rc;
+      if ((rc = enqueue_adjoint_step(c, args_of(s)))) return rc;
+  }
+  if (rw) {
+    launch_readout_adjoint(c->S, c->W, RA, 1, c->stream);
+    HIPCHK(c, hipGetLastError());
+    c->rw_launches = 2;
   }
   if (launches) *launches = fused ? 1 : nsteps;
   return DC_OK;
@@ -631,6 +696,7 @@ int kernel_time_end(dc_ctx *c, bool bwd, int launches) {
   const int chunks = (bwd ? use_cluster_bwd(c) : use_cluster_fwd(c)) ? (c->B + c->cl.nb - 1) / c->cl.nb : 1;
   (bwd ? c->bwd_ms : c->fwd_ms) += ms;
   (bwd ? c->bwd_launches : c->fwd_launches) += (bwd && (c->params.adjoint_mode == 2 || c->params.adjoint_mode == 3)) ? c->dense_launches - c->dense_mark : launches * chunks;
+  if (bwd) c->bwd_launches += c->rw_launches;      // the read-out's seed and parameter passes, when the sweep ran them
   return cluster_check(c);
 }
 
@@ -1097,6 +1163,7 @@ int dc_alloc_batch(dc_ctx *c, int B, int tape) {
     c->ps_built = pb;
   }
   c->SEEDX = c->SEEDV = nullptr;
+  c->RWJ = c->RWW = c->RSX = c->RSV = nullptr; c->rw_has = nullptr; c->sched_rw.assign(slots + 1, 0); c->rw_arrived = -1;      // read-out weights: allocated by their first setter
   c->INJ_X = c->INJ_F = c->INJ_N = c->INJ_SN = c->INJ_SD = nullptr; c->inj_slot = -1;
   c->YS = nullptr; c->keep_y = false;
   c->sched_xf.assign(slots + 1, 0); c->sched_fu.assign(slots + 1, 0); c->sched_fvs.assign(slots + 1, 0); c->sched_seed.assign(slots + 1, 0);
@@ -1476,6 +1543,7 @@ int dc_rollout_forward(dc_ctx *c, int slot, int nsteps) {
 int dc_seed_gradient(dc_ctx *c, int slot, const double *target, double scale_x) {
   int rc = check_batch(c, slot, slot);
   if (rc) return rc;
+  c->rw_arrived = -1;
   HIPCHK(c, hipSetDevice(c->device));
   const int N = c->host.N;
   std::vector<float> t(3 * (size_t) N);
@@ -1586,7 +1654,7 @@ int dc_clear_schedules(dc_ctx *c) {
   std::fill(c->sched_pc.begin(), c->sched_pc.end(), 0);      // (the rows keep their entries until a step overwrites them: pc_row_gen = -1)
   std::fill(c->sched_pv.begin(), c->sched_pv.end(), 0); std::fill(c->sched_pw.begin(), c->sched_pw.end(), 0);
   std::fill(c->sched_ps.begin(), c->sched_ps.end(), 0);      // (like the centres: the rows keep their entries until a step overwrites them, ps_row_gen = -1)
-  return DC_OK;
+  return clear_readout_gradients(c);
 }
 
 // ---- movable obstacles: per-rollout, per-step offsets of the primitive groups' centres (dc_primoffset.h holds the rule). The reference reads
@@ -1950,6 +2018,7 @@ int dc_set_gradient(dc_ctx *c, const double *dL_dx, const double *dL_dv) {
   int rc = check_batch(c, 0, 0);
   if (rc) return rc;
   if (!dL_dx || !dL_dv) return fail(c, DC_ERR_INVALID, "dc_set_gradient: null gradient");
+  c->rw_arrived = -1;      // a gradient from outside: no chain
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = h2d_planar(c, dL_dx, c->GX, c->host.N, true))) return rc;
   if ((rc = h2d_planar(c, dL_dv, c->GV, c->host.N, true))) return rc;
@@ -2063,6 +2132,7 @@ int dc_set_gradient_dev(dc_ctx *c, const void *d_dL_dx, const void *d_dL_dv, int
   int rc = check_batch(c, 0, 0);
   if (rc) return rc;
   if (!d_dL_dx || !d_dL_dv) return fail(c, DC_ERR_INVALID, "dc_set_gradient_dev: null gradient");
+  c->rw_arrived = -1;
   HIPCHK(c, hipSetDevice(c->device));
   launch_rows_to_planar(d_dL_dx, is_f32, c->GX, c->B, c->host.N, c->d_user_of, c->stream);
   launch_rows_to_planar(d_dL_dv, is_f32, c->GV, c->B, c->host.N, c->d_user_of, c->stream);
@@ -2180,6 +2250,76 @@ int dc_get_contact_readout(dc_ctx *c, int slot0, int nslots, int *state, double 
   if (wrench) HIPCHK(c, hipMemcpyAsync(wrench, dw.p, nw * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return cluster_check(c);
+}
+
+// ---- gradients of a loss on the contact read-out (dc_readout_adjoint.hip) ----
+namespace {
+int readout_gradients_check(dc_ctx *c, const char *who, int slot0, int nslots, const void *jn, const void *wrench) {
+  if (!c) return DC_ERR_INVALID;
+  const std::string w(who);
+  if (!jn && !wrench) {      // clear
+    if (!c->built) return fail(c, DC_ERR_STATE, "dc_build has not been called");
+    if (c->B <= 0) return fail(c, DC_ERR_STATE, w + ": dc_alloc_batch has not been called");
+    return DC_OK;
+  }
+  if (slot0 < 1) return fail(c, DC_ERR_INVALID, w + ": slot 0 has no record");
+  if (nslots < 1) return fail(c, DC_ERR_INVALID, w + ": nslots < 1");
+  if (!c->built) return fail(c, DC_ERR_STATE, "dc_build has not been called");
+  if (wrench && c->ngroups < 1) return fail(c, DC_ERR_INVALID, w + ": wrench weights given to a context with no primitive group");
+  if (c->B > 0 && (long) slot0 + nslots - 1 > c->tape) return fail(c, DC_ERR_INVALID, w + ": slots " + std::to_string(slot0) + " .. " + std::to_string((long) slot0 + nslots - 1) + " reach past the tape of " + std::to_string(c->tape) + " steps");
+  return check_batch(c, slot0, slot0 + nslots - 1);
+}
+// the weights of records slot0 .. slot0 + nslots - 1 from DEVICE buffers, enqueued; a null pointer = zeros for those records
+int readout_gradients_enqueue(dc_ctx *c, int slot0, int nslots, const void *d_jn, const void *d_wrench, int is_f32) {
+  int rc;
+  const int N = c->host.N, G = std::max(c->ngroups, 1);
+  const size_t slots = (size_t) c->tape + 1, pj = (size_t) c->B * N, pw = (size_t) c->B * G * kWrenchRow, se = slot_elems(c);
+  if (!c->RSV) {      // (RSV is the last of the five: a failed allocation leaves it null and the next call starts over)
+    auto &pool = c->batch_allocs;
+    if ((rc = dev_alloc(c, pool, &c->RWJ, pj * slots))) return rc;
+    if ((rc = dev_alloc(c, pool, &c->RWW, pw * slots))) return rc;
+    if ((rc = dev_alloc(c, pool, &c->rw_has, slots))) return rc;
+    if ((rc = dev_alloc(c, pool, &c->RSX, se * slots))) return rc;
+    if ((rc = dev_alloc(c, pool, &c->RSV, se * slots))) return rc;
+  }
+  if (d_jn) launch_vertex_rows_in(d_jn, is_f32, c->RWJ + pj * slot0, (long) nslots * c->B, N, c->d_user_of, c->stream);
+  else HIPCHK(c, hipMemsetAsync(c->RWJ + pj * slot0, 0, sizeof(float) * pj * nslots, c->stream));
+  if (d_wrench) launch_cast_in(d_wrench, is_f32, c->RWW + pw * slot0, (long) (pw * nslots), c->stream);
+  else HIPCHK(c, hipMemsetAsync(c->RWW + pw * slot0, 0, sizeof(float) * pw * nslots, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->rw_has + slot0, 1, (size_t) nslots, c->stream));
+  HIPCHK(c, hipGetLastError());
+  for (int k = 0; k < nslots; k++) c->sched_rw[slot0 + k] = 1;
+  c->rw_arrived = -1;
+  return DC_OK;
+}
+}  // namespace
+
+int dc_set_contact_readout_gradients_dev(dc_ctx *c, int slot0, int nslots, const void *d_dL_djn, const void *d_dL_dwrench, int is_f32) {
+  int rc = readout_gradients_check(c, "dc_set_contact_readout_gradients_dev", slot0, nslots, d_dL_djn, d_dL_dwrench);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!d_dL_djn && !d_dL_dwrench) return clear_readout_gradients(c);
+  return readout_gradients_enqueue(c, slot0, nslots, d_dL_djn, d_dL_dwrench, is_f32);
+}
+
+int dc_set_contact_readout_gradients(dc_ctx *c, int slot0, int nslots, const double *dL_djn, const double *dL_dwrench) {
+  int rc = readout_gradients_check(c, "dc_set_contact_readout_gradients", slot0, nslots, dL_djn, dL_dwrench);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!dL_djn && !dL_dwrench) return clear_readout_gradients(c);
+  const size_t nj = (size_t) nslots * c->B * c->host.N, nw = (size_t) nslots * c->B * c->ngroups * kWrenchRow;
+  ReadoutStage dj, dw;
+  if (dL_djn) {
+    HIPCHK(c, hipMalloc(&dj.p, nj * sizeof(double)));
+    HIPCHK(c, hipMemcpyAsync(dj.p, dL_djn, nj * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
+  if (dL_dwrench) {
+    HIPCHK(c, hipMalloc(&dw.p, nw * sizeof(double)));
+    HIPCHK(c, hipMemcpyAsync(dw.p, dL_dwrench, nw * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
+  if ((rc = readout_gradients_enqueue(c, slot0, nslots, dj.p, dw.p, 0))) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return DC_OK;
 }
 
 int dc_set_mu_dev(dc_ctx *c, const void *d_mu, int is_f32) {

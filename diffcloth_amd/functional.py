@@ -285,9 +285,10 @@ def _np64(t):
 class RolloutFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, sim, T, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets=None, primitive_velocities=None,
-                primitive_shapes=None, primitive_spins=None):
+                primitive_shapes=None, primitive_spins=None, contact_readout=False):
         e = sim.engine
         B, N = e.B, e.N
+        ctx.contact_readout = bool(contact_readout)
         if primitive_offsets is not None and primitive_offsets.dim() == 3:      # constant over the episode: the same entry in every step
             primitive_offsets = primitive_offsets.detach().unsqueeze(0).expand(T, *primitive_offsets.shape)
         ctx.velocities_per_episode = primitive_velocities is not None and primitive_velocities.dim() == 3      # (its gradient: summed over the steps)
@@ -329,6 +330,11 @@ class RolloutFunction(torch.autograd.Function):
             vs = torch.empty_like(xs)
             e.get_states_dev(1, T, xs, vs)
             sim.step_idx = T
+            if ctx.contact_readout:
+                jn = torch.empty((T, B, N), dtype=x0.dtype, device=x0.device)
+                wr = torch.empty((T, B, e.ngroups, 10), dtype=x0.dtype, device=x0.device)
+                e.contact_readout_dev(1, T, None, jn, wr)
+                return xs, vs, jn, wr
             return xs, vs
         e.set_trajectory_start(0)
         e.clear_schedules()
@@ -352,10 +358,14 @@ class RolloutFunction(torch.autograd.Function):
         e.rollout_forward(0, T)
         xs, vs = e.get_states(1, T)
         sim.step_idx = T
+        if ctx.contact_readout:
+            ro = e.contact_readout(1, T, state=False)
+            return (torch.as_tensor(xs).to(x0.dtype), torch.as_tensor(vs).to(x0.dtype), torch.as_tensor(ro["normal_impulse"]).to(x0.dtype),
+                    torch.as_tensor(ro["wrench"]).to(x0.dtype))
         return torch.as_tensor(xs).to(x0.dtype), torch.as_tensor(vs).to(x0.dtype)
 
     @staticmethod
-    def backward(ctx, grad_xs, grad_vs):
+    def backward(ctx, grad_xs, grad_vs, grad_jn=None, grad_wrench=None):
         sim, T = ctx.sim, ctx.T
         e = sim.engine
         B, N, Af, G = e.B, e.N, e.Af, e.ngroups
@@ -377,7 +387,13 @@ class RolloutFunction(torch.autograd.Function):
             if T > 1:
                 e.set_seed_schedule_dev(1, T - 1, gxs[:T - 1], gvs[:T - 1])
             e.set_gradient_dev(gxs[T - 1], gvs[T - 1])
-            e.rollout_backward_async(T, T)
+            if ctx.contact_readout:        # the loss's gradient w.r.t. the read-out: the sweep adds its part to every gradient it leaves
+                e.set_contact_readout_gradients_dev(1, T, grad_jn.detach().to(dt).contiguous(), grad_wrench.detach().to(dt).contiguous())
+            try:
+                e.rollout_backward_async(T, T)
+            finally:
+                if ctx.contact_readout:          # (a sweep that raises must not leave the weights on the context)
+                    e.set_contact_readout_gradients_dev(1, T, None, None)
             new = lambda *shape: torch.empty(shape, dtype=dt, device=dev)
             dx0, dv0 = new(B, 3 * N), new(B, 3 * N)
             dmu = new(B, G) if need_mu else None
@@ -404,13 +420,19 @@ class RolloutFunction(torch.autograd.Function):
                 if ctx.spins_per_episode:
                     dom = dom.sum(0)
             sim.check_episode()                # the single synchronisation of the episode: errors of both sweeps surface here
-            return None, None, dx0, dv0, da, dfu, dfvs, dfv, dmu, None, dw, None, dom
+            return None, None, dx0, dv0, da, dfu, dfvs, dfv, dmu, None, dw, None, dom, None
         gxs, gvs = _np64(grad_xs), _np64(grad_vs)
         e.keep_force_gradients(keep)
         zero = np.zeros((1, B, 3 * N))
         e.set_seed_schedule(0, np.concatenate([zero, gxs[:T - 1]]), np.concatenate([zero, gvs[:T - 1]]))
         e.set_gradient(gxs[T - 1], gvs[T - 1])
-        e.rollout_backward(T, T)
+        if ctx.contact_readout:
+            e.set_contact_readout_gradients(1, _np64(grad_jn), _np64(grad_wrench))
+        try:
+            e.rollout_backward(T, T)
+        finally:
+            if ctx.contact_readout:
+                e.set_contact_readout_gradients(1, None, None)
         dx0, dv0, dmu = e.get_gradient()
         t = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(dt)
         da = t(e.get_dxfixed(1, T)) if need_a else None
@@ -432,12 +454,21 @@ class RolloutFunction(torch.autograd.Function):
             dom = e.get_primitive_spin_gradients(1, T)
             dom = t(dom.sum(0) if ctx.spins_per_episode else dom)
         sim.check_episode()
-        return None, None, t(dx0), t(dv0), da, dfu, dfvs, dfv, (t(dmu) if need_mu else None), None, dw, None, dom
+        return None, None, t(dx0), t(dv0), da, dfu, dfvs, dfv, (t(dmu) if need_mu else None), None, dw, None, dom, None
 
 
 def sim_rollout(sim, x0, v0, actions=None, *, steps=None, uniform_force=None, vertex_force_scale=None, vertex_forces=None, mu=None,
-                primitive_offsets=None, primitive_velocities=None, primitive_shapes=None, primitive_spins=None):
+                primitive_offsets=None, primitive_velocities=None, primitive_shapes=None, primitive_spins=None, contact_readout=False):
     """A whole differentiable episode of all rollouts: the states after every step, (xs, vs), [T, B, 3N] each in the dtype of x0.
+
+    contact_readout=True returns (xs, vs, jn, wrench): the contact read-out of every step as DIFFERENTIABLE outputs, jn [T, B, N] the normal
+    impulse per vertex and wrench [T, B, G, 10] the row {J[3], tau[3], sum jn, take-off, stick, slide counts} per primitive group
+    (BatchedSim.contact_readout describes them), in the dtype of x0, on the device path and on the host path. A loss on them back-propagates
+    to every tensor argument that receives a gradient — x0, v0, actions, the forces, mu, primitive_velocities, primitive_spins: the
+    backward pass hands the incoming jn and wrench gradients to Engine.set_contact_readout_gradients[_dev] before the sweep and clears them
+    afterwards. The contact set, the normals and the groups' centres are held constant, as everywhere in the adjoint, and the counts
+    (entries 7..9) carry no derivative. The default returns (xs, vs) exactly as before. `sim_step` has no such output: the per-step
+    function is out of scope for the read-out's gradient (use Engine.set_contact_readout_gradients with Engine.step_backward there).
 
     x0, v0: [B, 3N] initial state. actions: [T, B, 3 Af] clip targets of every step. uniform_force: [T, B, 3] force on every vertex per
     step. vertex_forces: [B, 3N] per-vertex force field, vertex_force_scale: [T, B] its factor per step (1 when omitted; the field is the
@@ -485,8 +516,12 @@ def sim_rollout(sim, x0, v0, actions=None, *, steps=None, uniform_force=None, ve
     `sim_step`, which mirrors the reference's per-step function (functional.py:88-97)."""
     T = _rollout_steps(sim, steps, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets, primitive_velocities,
                        primitive_shapes, primitive_spins)
+    if not isinstance(contact_readout, (bool, np.bool_)):
+        raise ValueError(f"sim_rollout: contact_readout must be True or False, got {type(contact_readout).__name__}")
+    if contact_readout and sim.engine.nprims < 1:
+        raise ValueError("sim_rollout: contact_readout=True, but the scene has no primitive: there is no contact to read out")
     return RolloutFunction.apply(sim, T, x0, v0, actions, uniform_force, vertex_force_scale, vertex_forces, mu, primitive_offsets,
-                                 primitive_velocities, primitive_shapes, primitive_spins)
+                                 primitive_velocities, primitive_shapes, primitive_spins, bool(contact_readout))
 
 
 def rotated_primitive_shapes(shapes, R):

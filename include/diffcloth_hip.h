@@ -508,13 +508,54 @@ int dc_get_force_schedule_gradients_dev(dc_ctx *ctx, int slot0, int nslots, void
  * Per-vertex outputs are in the caller's vertex numbering. Sums run in fp64 in a fixed order without atomics and are rounded once:
  * bit-reproducible. Each output may be NULL and is then not computed; all three NULL is DC_ERR_INVALID, as are slot0 < 1, nslots < 1, a
  * range past the tape, and a wrench pointer on a context with no primitive group. A record handed in with dc_set_record is read like any
- * other (its fp32 values). The outputs carry no derivative.
+ * other (its fp32 values). The outputs themselves carry no derivative; dc_set_contact_readout_gradients takes a loss's gradient with respect to them.
  * The host form copies back through device buffers of its own and synchronises. The _dev form only enqueues: d_state is int32, the other two
  * fp32 (is_f32 = 1) or fp64; nothing crosses PCIe.                                                                                   */
 int dc_get_contact_readout(dc_ctx *ctx, int slot0, int nslots, int *state /*nslots*B*N or NULL*/,
                            double *normal_impulse /*nslots*B*N or NULL*/, double *wrench /*nslots*B*num_groups*10 or NULL*/);
 int dc_get_contact_readout_dev(dc_ctx *ctx, int slot0, int nslots, void *d_state /*int32, nslots*B*N or NULL*/, void *d_normal_impulse /*nslots*B*N or NULL*/,
                                void *d_wrench /*nslots*B*num_groups*10 or NULL*/, int is_f32);
+/* Gradients of a loss on the contact read-out. dL_djn[k][b][i] and dL_dwrench[k][b][g][0..9] are the derivatives of a loss with respect to
+ * normal_impulse and wrench of the records slot0 .. slot0 + nslots - 1 as dc_get_contact_readout reports them (vertex numbering: the caller's;
+ * entries 7..9 of a wrench row, the counts, are ignored). They stay set, per slot, until they are overwritten or cleared, and every backward step
+ * that passes through such a record — dc_rollout_backward[_async] and dc_step_backward[_dev]; fused and unfused sweeps, records handed in with
+ * dc_set_record, adjoint_mode 0..3, split launches — adds the read-out's part to everything it leaves: dL_dx / dL_dv, dL_dmu, dL_dxfixed, the
+ * parameter gradients (dc_get_param_gradients), the force gradients (dc_get_force_gradient[s], dc_get_force_schedule_gradients_dev) and
+ * {dL/dw, dL/domega}. THE RULE, for a vertex i in contact with a primitive of group g in the step that produced record s, with J^, tau^, S^ the
+ * weights of J, tau and sum jn of group g and jn^_i that of the vertex's impulse:
+ *     phi_i = -J^ - tau^ x (x_i - c_g) + (jn^_i + S^) n_i        q_i = (dr_p,i/dd_i)^T phi_i  (take-off: 0, stick: -phi_i; 0 at every other vertex)
+ * c_g and n_i are held constant, as everywhere in the adjoint; the friction case is the one the read-out reports (current mu, the record's motion
+ * row) — with ONE exception: for a record handed in with dc_set_record the case is decided in fp64 on the handed-in values, as the adjoint's
+ * fp64 operator decides it for such a record, so that the seeds and the operator they enter differentiate the same law; the read-out reads that
+ * record's fp32 values, and within fp32 rounding of a boundary of the friction law (1e-6 |d|) the two can differ. r_p depends on f alone, before the self-contact layers, so the backward step through record s is the plain step with
+ *   1. dL/dx at slot s      += -(1/h) h^2 (A - dp/dx)^T A q - r_p,i x tau^    (the adjoint's fp64 element operator at the same x_new, without contact
+ *                                                                               part and mass term; the direct dependence of tau on x_i)
+ *   2. dL/dv at slot s - 1  += m_i q_i
+ *   3. y~ = y + q / h wherever y = (I + dr_df)^T u is read: the force gradients, dL_dxfixed, the dL/dk sums, the w = y - u term of dL_ddensity
+ *      (adddr_dd = false as before)
+ *   4. u_i + phi_i / h wherever u_i multiplies a primitive-contact derivative: dL_dmu[g] += sum (dr_p,i/dmu) . phi_i, dL/dw[g] += -sum m_i q_i,
+ *      dL/domega[g] += -sum m_i radius_p (n_i x q_i) for a DC_PRIM_SPHERE
+ * Items 1 and 2 are added to the loss gradients the sweep already takes, in rows of the engine's own that start as the caller's entries (the seed
+ * schedule, or dL_dxinit / dL_dvinit of a per-step call, or zeros): the caller's schedule is never modified, and gradient clipping, where
+ * enabled, acts on the total. WHICH CALL ADDS ITEM 1: the gradient a backward call leaves is that of the state it ARRIVES at, slot - nsteps, and
+ * holds item 1 of the record of that state when it carries weights (added to that state's seed row, like those of the states above it). A call
+ * that starts where the previous backward call on the context arrived — a chain of dc_step_backward calls handing dL_dx on as dL_dxnew, or of
+ * sweeps carrying the gradient on the device — therefore finds item 1 of its top record in what it is given; every other call adds it to the
+ * carried gradient itself. A chain is broken, and the next call adds its top record's part, by dc_set_gradient[_dev], dc_seed_gradient, any
+ * forward step, this setter, dc_clear_schedules and dc_alloc_batch; a caller who passes an UNRELATED dL_dxnew to dc_step_backward for exactly
+ * the record the previous call arrived at calls this setter (or dc_set_gradient) first. With this rule a fused sweep and the chain of per-step
+ * calls over the same tape give the same dL_dx, dL_dv, parameter rows and force gradients bit for bit. Items 3 and 4 are added after the steps to what
+ * they left. All of it is fp64 arithmetic on the fp32 record with sums in a fixed order, no atomics, rounded once: the same sweep twice gives the
+ * same bits. All-zero weights, weights never set and weights cleared give the same gradients, and a sweep none of whose records carries weights
+ * enqueues no additional kernel. There is no gradient through the contact set, the normals, the centres, the shapes or the counts.
+ * One pointer NULL: zeros for those slots; both NULL (slot0, nslots ignored) clears all weights, as dc_clear_schedules and dc_alloc_batch do.
+ * DC_ERR_INVALID: slot0 < 1, nslots < 1, a range past the tape, wrench weights on a context with no primitive group; a host-only context answers
+ * DC_ERR_STATE. Costs two tape-sized fp32 arrays and the weight tables, allocated by the first call after dc_alloc_batch.
+ * The host form synchronises; the _dev form takes DEVICE pointers (fp32 or fp64, any element alignment) and only enqueues.                    */
+int dc_set_contact_readout_gradients(dc_ctx *ctx, int slot0, int nslots, const double *dL_djn /*nslots*B*N or NULL*/,
+                                     const double *dL_dwrench /*nslots*B*num_groups*10 or NULL*/);
+int dc_set_contact_readout_gradients_dev(dc_ctx *ctx, int slot0, int nslots, const void *d_dL_djn /*nslots*B*N or NULL*/,
+                                         const void *d_dL_dwrench /*nslots*B*num_groups*10 or NULL*/, int is_f32);
 /* dc_set_mu (d_mu must not be NULL: dc_set_mu(NULL) restores the defaults) and dc_set_vertex_forces (NULL = none) from device buffers */
 int dc_set_mu_dev(dc_ctx *ctx, const void *d_mu /*B*num_groups*/, int is_f32);
 int dc_set_vertex_forces_dev(dc_ctx *ctx, const void *d_f /*B*3N or NULL*/, int is_f32);
