@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libdiffcloth_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-ENGINE_SOURCES = ["dc_forward.hip", "dc_forward_res.hip", "dc_forward_pk.hip", "dc_forward_pk_tpl.hip", "dc_forward_pk_defl.hip", "dc_forward_cl.hip", "dc_forward_cl_defl.hip", "dc_adjoint.hip", "dc_adjoint_moving.hip", "dc_adjoint_cl.hip", "dc_adjoint_cl_moving.hip", "dc_adjoint_dense.hip", "dc_adjoint_band.hip", "dc_selfcontact.hip", "dc_convert.hip", "dc_boundary.hip", "dc_readout.hip", "dc_readout_adjoint.hip", "dc_engine.hip", "dc_comm.cpp", "dc_tables.cpp", "dc_clusterplan.cpp", "dc_record.cpp", "dc_system.cpp", "dc_windows.cpp", "dc_packets.cpp", "dc_dense.cpp", "dc_deflate.cpp", "dc_spheremesh.cpp"]
+ENGINE_SOURCES = ["dc_forward.hip", "dc_forward_res.hip", "dc_forward_pk.hip", "dc_forward_pk_tpl.hip", "dc_forward_pk_defl.hip", "dc_forward_cl.hip", "dc_forward_cl_defl.hip", "dc_adjoint.hip", "dc_adjoint_moving.hip", "dc_adjoint_cl.hip", "dc_adjoint_cl_moving.hip", "dc_adjoint_dense.hip", "dc_adjoint_band.hip", "dc_selfcontact.hip", "dc_convert.hip", "dc_boundary.hip", "dc_readout.hip", "dc_self_readout.hip", "dc_readout_adjoint.hip", "dc_engine.hip", "dc_comm.cpp", "dc_tables.cpp", "dc_clusterplan.cpp", "dc_record.cpp", "dc_system.cpp", "dc_windows.cpp", "dc_packets.cpp", "dc_dense.cpp", "dc_deflate.cpp", "dc_spheremesh.cpp"]
 
 # sources that include another translation unit of csrc as text (the same kernels compiled once more under a switch)
 INCLUDED_AS_TEXT = {"dc_adjoint_moving.hip": ["dc_adjoint.hip"], "dc_adjoint_cl_moving.hip": ["dc_adjoint_cl.hip"]}

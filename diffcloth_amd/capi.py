@@ -75,6 +75,7 @@ EXPORTED_SYMBOLS = [
     "dc_get_primitive_shapes",
     "dc_get_contact_readout", "dc_get_contact_readout_dev",
     "dc_set_contact_readout_gradients", "dc_set_contact_readout_gradients_dev",
+    "dc_get_self_contact_readout", "dc_get_self_contact_readout_dev",
 ]
 
 _lib = None
@@ -92,6 +93,10 @@ def load_library():
         lib = C.CDLL(path)
         lib.dc_last_error.restype = C.c_char_p
         lib.dc_version.restype = C.c_char_p
+        lib.dc_get_self_contact_readout.restype = C.c_int
+        lib.dc_get_self_contact_readout.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.dc_get_self_contact_readout_dev.restype = C.c_int
+        lib.dc_get_self_contact_readout_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         _lib = lib
     return _lib
 
@@ -480,6 +485,56 @@ class Engine:
         slot0, nslots = self._readout_range(slot0, nslots)
         (pj, pw), f = self._tps((dL_djn, self.B * self.N, nslots), (dL_dwrench, self.B * self.ngroups * 10, nslots))
         self._chk(self.lib.dc_set_contact_readout_gradients_dev(self.h, C.c_int(slot0), C.c_int(nslots), pj, pw, C.c_int(f)))
+
+    @property
+    def max_self_contacts(self):
+        """entries of a rollout's self-contact list as dc_build sizes it: dc_params::max_self_contacts, max(2048, N) where that is 0, at most 16000"""
+        m = int(self.params.max_self_contacts)
+        return min(m if m > 0 else max(2048, self.N), 16000)
+
+    def _self_readout_range(self, who, slot0, nslots, cap, listed):
+        slot0, nslots = int(slot0), int(nslots)
+        if slot0 < 1:
+            raise ValueError(f"{who}: slot 0 has no record (slot0 >= 1)")
+        if nslots < 1:
+            raise ValueError(f"{who}: nslots must be >= 1")
+        cap = self.max_self_contacts if cap is None else int(cap)
+        if listed and cap < 1:
+            raise ValueError(f"{who}: cap must be >= 1 where pairs or impulse is asked for")
+        return slot0, nslots, max(cap, 0)
+
+    def self_contact_readout(self, slot0, nslots=1, cap=None, pairs=True, impulse=True, vertex_impulse=True, totals=True):
+        """dc_get_self_contact_readout of the records slot0 .. slot0 + nslots - 1: dict(pairs [nslots][B][cap][4] int32 = {id1, id2, layer,
+        state} — state 1 take-off, 2 stick, 3 slide; {-1, -1, -1, 0} behind the list —, impulse [nslots][B][cap][4] = {r_k, jn_k}, r_k the
+        impulse on id1 (id2 receives -r_k), vertex_impulse [nslots][B][N][3] = the per-vertex sums, totals [nslots][B][8] = {contacts, layers,
+        distinct vertices, sum jn, sum |r_T|, take-off, stick, slide}). cap None = the context's max_self_contacts. Each output can be
+        switched off (its entry is then None); the call synchronises. The outputs carry no gradient."""
+        if not (pairs or impulse or vertex_impulse or totals):
+            raise ValueError("self_contact_readout: nothing asked for")
+        slot0, nslots, cap = self._self_readout_range("self_contact_readout", slot0, nslots, cap, pairs or impulse)
+        p = np.zeros((nslots, self.B, cap, 4), dtype=np.int32) if pairs else None
+        r = np.zeros((nslots, self.B, cap, 4)) if impulse else None
+        v = np.zeros((nslots, self.B, self.N, 3)) if vertex_impulse else None
+        t = np.zeros((nslots, self.B, 8)) if totals else None
+        self._chk(self.lib.dc_get_self_contact_readout(self.h, slot0, nslots, cap, _i(p), _d(r), _d(v), _d(t)))
+        return dict(pairs=p, impulse=r, vertex_impulse=v, totals=t)
+
+    def self_contact_readout_dev(self, slot0, nslots, cap, pairs=None, impulse=None, vertex_impulse=None, totals=None):
+        """dc_get_self_contact_readout_dev into CUDA tensors: pairs int32 [nslots][B][cap][4], impulse [nslots][B][cap][4], vertex_impulse
+        [nslots][B][N][3] and totals [nslots][B][8] of one floating dtype; None skips an output. Only enqueued on the context's stream."""
+        import torch
+        if pairs is None and impulse is None and vertex_impulse is None and totals is None:
+            raise ValueError("self_contact_readout_dev: nothing asked for")
+        slot0, nslots, cap = self._self_readout_range("self_contact_readout_dev", slot0, nslots, cap, pairs is not None or impulse is not None)
+        pp = None
+        if pairs is not None:
+            if not pairs.is_cuda or not pairs.is_contiguous() or pairs.dtype != torch.int32 or pairs.numel() != nslots * self.B * cap * 4:
+                raise ValueError(f"pairs: expected a contiguous CUDA int32 tensor of {nslots * self.B * cap * 4} elements, got {pairs.dtype} {tuple(pairs.shape)} on {pairs.device}")
+            if pairs.device.index != self.device:
+                raise ValueError(f"tensor on cuda:{pairs.device.index}, the engine runs on device {self.device}")
+            pp = C.c_void_p(pairs.data_ptr())
+        (pi, pv, pt), f = self._tps((impulse, self.B * cap * 4, nslots), (vertex_impulse, self.B * self.N * 3, nslots), (totals, self.B * 8, nslots))
+        self._chk(self.lib.dc_get_self_contact_readout_dev(self.h, slot0, nslots, cap, pp, pi, pv, pt, f))
 
     def get_self_contacts(self, slot, rollout=0, cap=8192):
         cnt = C.c_int(); nl = C.c_int()

@@ -80,6 +80,10 @@ struct dc_ctx {
   std::vector<char> sched_rw;
   int rw_arrived = -1;              // the state the last backward call arrived at when the gradient it left holds the read-out's part of that record; -1 = none
   int rw_launches = 0;              // launches of the read-out's adjoint passes in the sweep being enqueued (dc_kernel_times counts them)
+  // self-contact read-out (dc_get_self_contact_readout): the planes of the global-memory walk, allocated by the first call after dc_alloc_batch
+  // whose LDS plan (dc_self_readout.h) cannot hold every possible record; null otherwise
+  float *sro_scratch = nullptr;     // [B][3][N] g - f
+  double *sro_sums = nullptr;       // [B][3][N] per-vertex sums
   // movable obstacles (dc_set_primitive_offsets / dc_set_primitive_offset_schedule, dc_primoffset.h): absolute fp32 centres of the P flattened
   // primitives. Every row of PC is valid at all times — the built centres until something else is written — and the forward kernels always
   // read the row of the slot their step produces, so a slot says where its obstacle was (dc_get_primitive_centers).

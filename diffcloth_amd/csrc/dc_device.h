@@ -296,5 +296,11 @@ void launch_dfv_scale(const float *ys, const float *fv, void *out, int is_f32, i
 void launch_contact_readout(const DevSystem &S, const float *X, const float *F, const float *NRM, const int *PRIM, const float *PC, const float *PV,
                             const float *mu, long rows, int B, int *state, void *jn, void *wrench, int is_f32, hipStream_t st);
 void launch_dfv(const float *ys, const float *w, void *out, int is_f32, int nslots, int B, int N, const int *user_of, double h2, hipStream_t st);
+// self-contact read-out (dc_self_readout.hip; arguments and LDS plan in dc_self_readout.h): rows A.row0 .. A.row0 + rows - 1 of a range of
+// records in ONE launch. pairs (int32 [..][cap_out][4]), impulse ([..][cap_out][4]), vertex_impulse ([..][N][3], caller's numbering) and
+// totals ([..][8]) are the pointers of the range's first row, each optional, any element alignment
+struct SelfRoArgs;
+hipError_t launch_self_readout(const DevSystem &S, const SelfRoArgs &A, long rows, int *pairs, void *impulse, void *vertex_impulse, void *totals,
+                               int is_f32, hipStream_t st);
 
 }  // namespace dc

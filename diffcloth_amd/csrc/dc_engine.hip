@@ -14,6 +14,7 @@
 #include "dc_primshape.h"
 #include "dc_readout_adjoint.h"
 #include "dc_record.h"
+#include "dc_self_readout.h"
 #include "dc_tables.h"
 #include "dc_spheremesh.h"
 #include "dc_selftmp.h"
@@ -1166,6 +1167,7 @@ int dc_alloc_batch(dc_ctx *c, int B, int tape) {
   c->RWJ = c->RWW = c->RSX = c->RSV = nullptr; c->rw_has = nullptr; c->sched_rw.assign(slots + 1, 0); c->rw_arrived = -1;      // read-out weights: allocated by their first setter
   c->INJ_X = c->INJ_F = c->INJ_N = c->INJ_SN = c->INJ_SD = nullptr; c->inj_slot = -1;
   c->YS = nullptr; c->keep_y = false;
+  c->sro_scratch = nullptr; c->sro_sums = nullptr;
   c->sched_xf.assign(slots + 1, 0); c->sched_fu.assign(slots + 1, 0); c->sched_fvs.assign(slots + 1, 0); c->sched_seed.assign(slots + 1, 0);
   if ((rc = dev_alloc(c, pool, &c->DMU, (size_t) B * G))) return rc;
   if ((rc = dev_alloc(c, pool, &c->target, (size_t) 3 * N))) return rc;
@@ -2248,6 +2250,74 @@ int dc_get_contact_readout(dc_ctx *c, int slot0, int nslots, int *state, double 
   if (state) HIPCHK(c, hipMemcpyAsync(state, ds.p, nv * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   if (normal_impulse) HIPCHK(c, hipMemcpyAsync(normal_impulse, dj.p, nv * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (wrench) HIPCHK(c, hipMemcpyAsync(wrench, dw.p, nw * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return cluster_check(c);
+}
+
+// ---- self-contact read-out (dc_self_readout.hip): per-pair impulses, per-vertex sums and totals of the records slot0 .. slot0 + nslots - 1
+namespace {
+int self_readout_check(dc_ctx *c, const char *who, int slot0, int nslots, int cap, const void *pairs, const void *impulse, const void *vimp,
+                       const void *totals) {
+  if (!c) return DC_ERR_INVALID;
+  const std::string w(who);
+  if (slot0 < 1) return fail(c, DC_ERR_INVALID, w + ": slot 0 has no record");
+  if (nslots < 1) return fail(c, DC_ERR_INVALID, w + ": nslots < 1");
+  if (!pairs && !impulse && !vimp && !totals) return fail(c, DC_ERR_INVALID, w + ": pairs, impulse, vertex_impulse and totals are all null");
+  if (cap < 1 && (pairs || impulse)) return fail(c, DC_ERR_INVALID, w + ": cap < 1 while pairs or impulse is asked for");
+  if (!c->built) return fail(c, DC_ERR_STATE, "dc_build has not been called");
+  if (c->B > 0 && (long) slot0 + nslots - 1 > c->tape) return fail(c, DC_ERR_INVALID, w + ": slots " + std::to_string(slot0) + " .. " + std::to_string((long) slot0 + nslots - 1) + " reach past the tape of " + std::to_string(c->tape) + " steps");
+  return check_batch(c, slot0, slot0 + nslots - 1);
+}
+// Enqueues the range: ONE launch when every record the context can hold fits the kernel's LDS plan; otherwise slot by slot, because the rows
+// that take the global-memory walk share the [B] scratch planes (allocated here, by the first such call after dc_alloc_batch).
+int self_readout_enqueue(dc_ctx *c, int slot0, int nslots, int cap, int *pairs, void *impulse, void *vimp, void *totals, int is_f32) {
+  const SelfRoPlan plan = selfro_plan(c->host.N, c->self_cap, selfro_lds_limit(kSelfRoLdsFloatsMax));
+  int rc;
+  if (plan.scratch && !c->sro_sums) {      // (sro_sums is the second of the two: a failed allocation leaves it null and the next call starts over)
+    if ((rc = dev_alloc(c, c->batch_allocs, &c->sro_scratch, slot_elems(c)))) return rc;
+    if ((rc = dev_alloc(c, c->batch_allocs, &c->sro_sums, slot_elems(c)))) return rc;
+  }
+  const size_t se = slot_elems(c), sp = (size_t) c->B * c->host.N;
+  SelfRoArgs A;
+  A.F = c->F + se * slot0; A.NRM = c->NRM + se * slot0; A.PRIM = c->PRIM + sp * slot0;
+  A.PV = c->PV ? pv_slot(c, slot0) : nullptr; A.mu = c->mu; A.R = self_slot(c, slot0);
+  A.B = c->B; A.row0 = 0; A.cap_out = std::max(cap, 0); A.lds_floats = plan.lds_floats;
+  A.scratch = plan.scratch ? c->sro_scratch : nullptr; A.sums = plan.scratch ? c->sro_sums : nullptr;
+  if (!plan.scratch) {
+    HIPCHK(c, launch_self_readout(c->S, A, (long) nslots * c->B, pairs, impulse, vimp, totals, is_f32, c->stream));
+    return DC_OK;
+  }
+  for (int k = 0; k < nslots; k++) {
+    A.row0 = k * c->B;
+    HIPCHK(c, launch_self_readout(c->S, A, c->B, pairs, impulse, vimp, totals, is_f32, c->stream));
+  }
+  return DC_OK;
+}
+}  // namespace
+
+int dc_get_self_contact_readout_dev(dc_ctx *c, int slot0, int nslots, int cap, void *d_pairs, void *d_impulse, void *d_vertex_impulse, void *d_totals,
+                                    int is_f32) {
+  int rc = self_readout_check(c, "dc_get_self_contact_readout_dev", slot0, nslots, cap, d_pairs, d_impulse, d_vertex_impulse, d_totals);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return self_readout_enqueue(c, slot0, nslots, cap, (int *) d_pairs, d_impulse, d_vertex_impulse, d_totals, is_f32);
+}
+
+int dc_get_self_contact_readout(dc_ctx *c, int slot0, int nslots, int cap, int *pairs, double *impulse, double *vertex_impulse, double *totals) {
+  int rc = self_readout_check(c, "dc_get_self_contact_readout", slot0, nslots, cap, pairs, impulse, vertex_impulse, totals);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t rows = (size_t) nslots * c->B, np = rows * (size_t) std::max(cap, 0) * 4, nv = rows * 3 * c->host.N, nt = rows * kSelfRoTotals;
+  ReadoutStage dp, di, dv, dt;
+  if (pairs) HIPCHK(c, hipMalloc(&dp.p, np * sizeof(int)));
+  if (impulse) HIPCHK(c, hipMalloc(&di.p, np * sizeof(double)));
+  if (vertex_impulse) HIPCHK(c, hipMalloc(&dv.p, nv * sizeof(double)));
+  if (totals) HIPCHK(c, hipMalloc(&dt.p, nt * sizeof(double)));
+  if ((rc = self_readout_enqueue(c, slot0, nslots, cap, (int *) dp.p, di.p, dv.p, dt.p, 0))) return rc;
+  if (pairs) HIPCHK(c, hipMemcpyAsync(pairs, dp.p, np * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (impulse) HIPCHK(c, hipMemcpyAsync(impulse, di.p, np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (vertex_impulse) HIPCHK(c, hipMemcpyAsync(vertex_impulse, dv.p, nv * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (totals) HIPCHK(c, hipMemcpyAsync(totals, dt.p, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return cluster_check(c);
 }

@@ -26,4 +26,8 @@ inline const KernelSwitches &kernel_switches() {
   return sw;
 }
 
+// DC_TEST_SELFRO_LDS: floats of LDS the self-contact read-out's kernel may plan with (dc_self_readout.h), read at every read-out call; not
+// set, 0 or negative = all a workgroup can have. A small value sends the rows through the kernel's global-memory walk.
+inline int selfro_lds_limit(int dflt) { const int v = env_int("DC_TEST_SELFRO_LDS", 0); return v > 0 ? v : dflt; }
+
 }  // namespace dc

@@ -117,6 +117,41 @@ class BatchedSim:
         e.contact_readout_dev(slot0, nslots, s, j, w)
         return dict(state=s, normal_impulse=j, wrench=w)
 
+    def self_contact_readout(self, slot0=1, nslots=None, cap=None, dtype=torch.float32, pairs=True, impulse=True, vertex_impulse=True, totals=True):
+        """What the cloth's sheets press on each other with in the steps of this episode (dc_get_self_contact_readout_dev): CUDA tensors of the
+        records slot0 .. slot0 + nslots - 1 (nslots None: up to the last step taken), formed on the engine's GPU on torch's current stream,
+        without a synchronisation. Usable after sim_step and after a sim_rollout forward pass.
+          pairs           int32 [nslots, B, cap, 4]: {id1, id2, layer, state} per self contact in the order of Engine.get_self_contacts; state 1
+                          take-off, 2 stick, 3 slide; {-1, -1, -1, 0} behind the list. cap None: the engine's max_self_contacts
+          impulse         [nslots, B, cap, 4]: {r_k (x, y, z), jn_k = r_k . n_k}; r_k acts on id1, -r_k on id2
+          vertex_impulse  [nslots, B, N, 3]: the sum of the +-r_k of the pairs a vertex is in, 0 elsewhere
+          totals          [nslots, B, 8]: contacts, layers, distinct vertices, sum jn, sum |r_k - jn_k n_k|, take-off / stick / slide counts
+        An output switched off is None. The outputs carry NO gradient (requires_grad is False): they are observations."""
+        e = self.engine
+        slot0 = int(slot0)
+        if slot0 < 1:
+            raise ValueError("self_contact_readout: slot 0 has no record (slot0 >= 1)")
+        if nslots is None:
+            nslots = self.step_idx - slot0 + 1
+        nslots = int(nslots)
+        if nslots < 1 or slot0 + nslots - 1 > self.step_idx:
+            raise ValueError(f"self_contact_readout: records {slot0} .. {slot0 + nslots - 1} asked for, the episode has taken {self.step_idx} step(s)")
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("self_contact_readout: dtype must be torch.float32 or torch.float64")
+        if not (pairs or impulse or vertex_impulse or totals):
+            raise ValueError("self_contact_readout: nothing asked for")
+        cap = e.max_self_contacts if cap is None else int(cap)
+        if (pairs or impulse) and cap < 1:
+            raise ValueError("self_contact_readout: cap must be >= 1 where pairs or impulse is asked for")
+        dev = torch.device("cuda", e.device)
+        self.on_current_stream(dev)
+        p = torch.empty((nslots, e.B, cap, 4), dtype=torch.int32, device=dev) if pairs else None
+        r = torch.empty((nslots, e.B, cap, 4), dtype=dtype, device=dev) if impulse else None
+        v = torch.empty((nslots, e.B, e.N, 3), dtype=dtype, device=dev) if vertex_impulse else None
+        t = torch.empty((nslots, e.B, 8), dtype=dtype, device=dev) if totals else None
+        e.self_contact_readout_dev(slot0, nslots, cap, p, r, v, t)
+        return dict(pairs=p, impulse=r, vertex_impulse=v, totals=t)
+
     def reset(self, x0, v0=None):
         """Start a new episode from the given states ([B, 3N]); returns them as float32 tensors like getStateInfo()."""
         if self.step_idx > 0:

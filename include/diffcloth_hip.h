@@ -556,6 +556,39 @@ int dc_set_contact_readout_gradients(dc_ctx *ctx, int slot0, int nslots, const d
                                      const double *dL_dwrench /*nslots*B*num_groups*10 or NULL*/);
 int dc_set_contact_readout_gradients_dev(dc_ctx *ctx, int slot0, int nslots, const void *d_dL_djn /*nslots*B*N or NULL*/,
                                          const void *d_dL_dwrench /*nslots*B*num_groups*10 or NULL*/, int is_f32);
+/* Self-contact read-out: what the cloth's sheets press on each other with. For the records slot0 .. slot0 + nslots - 1 (slot0 >= 1) the layered
+ * cloth-cloth friction of the step (Simulation.cpp:655-678) is re-formed on the device from the fp32 tape values; nothing is computed that the
+ * step did not compute. THE RULE, for record s of rollout b:
+ *   1. g_i = f_i + r_p,i at every vertex of the record's self-contact working set: f from the record, r_p,i the primitive part exactly as
+ *      dc_get_contact_readout re-forms it (prim_d with the motion row of s, the friction law with the context's CURRENT mu[b][group]), 0 where
+ *      the vertex is in no primitive contact.
+ *   2. The layers are walked in record order, the pairs of a layer in any order (they are vertex-disjoint: dc_record's contract). For pair
+ *      k = (A, B) with normal n_k:   d_k = g_A / m_A - g_B / m_B,   r_k = r(n_k, d_k, 0.1) / (1/m_A + 1/m_B)  (the reduced mass
+ *      m_A m_B / (m_A + m_B), formed as the step forms it),   state_k = the friction law's case on d_k,   then g_A += r_k, g_B -= r_k.
+ *      The device functions and the fp32 expressions are those of the step's layered pass.
+ *   3. r_self,i = sum of +-r_k over the pairs that contain i.
+ * The record's stored d per pair and its stored r are neither read nor written; a record handed in with dc_set_record is read like any other,
+ * through its fp32 values. Outputs, each optional (NULL = not computed):
+ *   pairs[k][b][c][0..3]          int32 {id1, id2, layer, state} of contact c, in the order of dc_get_self_contacts and in the caller's vertex
+ *                                 numbering; state 1 = take-off, 2 = stick, 3 = slide; entries c >= count hold {-1, -1, -1, 0}. `cap` = entries
+ *                                 per rollout; contacts beyond cap are not written but still enter the sums.
+ *   impulse[k][b][c][0..3]        {r_k (x, y, z), jn_k = r_k . n_k >= 0}: r_k is the impulse on id1, id2 receives -r_k; zeros beyond count
+ *   vertex_impulse[k][b][i][0..2] r_self,i in the caller's numbering, 0 at every other vertex (host form: nslots*B*3N doubles, xyz-interleaved)
+ *   totals[k][b][0..7]            {contacts evaluated, layers, distinct vertices, sum jn, sum |r_k - jn_k n_k|, take-off, stick, slide}
+ * All sums are fp64, run in a fixed order without atomics and are rounded once: bit-reproducible. A context without self-collision and a
+ * record without self contacts answer zeros (-1 ids). DC_ERR_INVALID: slot0 < 1, nslots < 1, a range past the tape, all four outputs NULL,
+ * cap < 1 while pairs or impulse is asked for; a host-only or unbuilt context answers DC_ERR_STATE.
+ * There is NO GRADIENT: the outputs carry no derivative and no setter takes a loss's gradient with respect to them (a later change).
+ * The host form stages through device buffers of its own and synchronises. The _dev form takes DEVICE pointers — pairs int32, the others
+ * fp32 (is_f32 = 1) or fp64, any element alignment — and only enqueues on the context's stream: no synchronisation, and no allocation
+ * after the first call (a context whose largest possible record does not fit one workgroup's LDS allocates two [B][3][N] scratch arrays
+ * then and enqueues the range slot by slot; otherwise the whole range is ONE launch).                                                  */
+int dc_get_self_contact_readout(dc_ctx *ctx, int slot0, int nslots, int cap, int *pairs /*nslots*B*cap*4 or NULL*/,
+                                double *impulse /*nslots*B*cap*4 or NULL*/, double *vertex_impulse /*nslots*B*3N or NULL*/,
+                                double *totals /*nslots*B*8 or NULL*/);
+int dc_get_self_contact_readout_dev(dc_ctx *ctx, int slot0, int nslots, int cap, void *d_pairs /*int32, nslots*B*cap*4 or NULL*/,
+                                    void *d_impulse /*nslots*B*cap*4 or NULL*/, void *d_vertex_impulse /*nslots*B*N*3 or NULL*/,
+                                    void *d_totals /*nslots*B*8 or NULL*/, int is_f32);
 /* dc_set_mu (d_mu must not be NULL: dc_set_mu(NULL) restores the defaults) and dc_set_vertex_forces (NULL = none) from device buffers */
 int dc_set_mu_dev(dc_ctx *ctx, const void *d_mu /*B*num_groups*/, int is_f32);
 int dc_set_vertex_forces_dev(dc_ctx *ctx, const void *d_f /*B*3N or NULL*/, int is_f32);
